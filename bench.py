@@ -6,19 +6,32 @@ A "step" = one pass of the hot path (rxg_classify_dev: the fused gfx950
 kernel) over one burst of synthetic frames already resident in HBM, plus at
 N > 1 the per-flow count all-reduce (the path's only exchange).
 Default workload = BASELINE configs[1] (64 B UDP, 1024 flows, 16M frames per
-GPU); configs[2..4] are measured in the same run and reported under
-"cfg3".."cfg5", BASELINE configs[0] (100K x 64 B UDP from a pcap, 1 flow)
-under "cfg1".
+GPU); with --full configs[2..4] are measured in the same run and reported
+under "cfg3".."cfg5", BASELINE configs[0] (100K x 64 B UDP from a pcap, 1
+flow) under "cfg1".
 
 N > 1 (one rank per GPU, weak scaling): every rank generates the GLOBAL burst
 of N x n frames, RSS-splits it on its GPU (rxg_rss_split_dev) and gathers its
 own shard (rxg_gather_dev) before the timed steps; a step classifies the shard
 and all-reduces the per-flow counts over RCCL (rxg_counts_allreduce); value =
-N x n frames / the max-over-ranks step time.  Every workload line carries a
-"parity" field: a seeded sample of the run's verdicts checked bit for bit
-against the oracle (the exit code is 3 if any differs).
+N x n frames / the max-over-ranks step time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2,cfg3]
+A plain run does only what the headline figure needs: it sets the headline
+workload (cfg2) up, ramps the clocks, runs the W warmup and the K timed steps,
+writes the outputs if --dump-outputs is given, and prints the result line.
+Everything else is behind --full: the other workloads (cfg3..cfg5, cfg1), the
+per-dispatch roofline pass and the slot-shape ceiling, the oracle parity sample
+and the golden digests, the count checks, the 8-B verdict and TX checksum legs,
+the CPU baselines, the socket-API rates, the measured HBM read ceiling and the
+detail file.  With --full every workload line carries a "parity" field: a
+seeded sample of the run's verdicts checked bit for bit against the oracle
+(the exit code is 3 if any differs).
+
+--dump-outputs DIR writes, after the timed steps, what the last step left with
+its caller (dump_outputs below): verdicts.npy, verdict_frames.npy, counts.npy.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py --full [--workload cfg2,cfg3] ...
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 """
 from __future__ import annotations
@@ -35,6 +48,10 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.join(ROOT, "dpdk-tcp-udp_protocol_stack_amd")
 sys.path.insert(0, PKG)
+
+# --workload's default: the headline alone, or with --full BASELINE configs[1..4]
+WORKLOADS_PLAIN = "cfg2"
+WORKLOADS_FULL = "cfg2,cfg3,cfg4,cfg5"
 
 
 def _gpus_arg(argv):
@@ -56,9 +73,9 @@ def _free_port():
 
 def _deadline_arg(argv):
     """--deadline S (seconds) from the command line; default from the
-    workload list: 120 s + 120 s per workload (a healthy N-rank run of the
-    default four workloads takes a few minutes at most)"""
-    wl = "cfg2,cfg3,cfg4,cfg5"
+    workload list: 120 s + 120 s per workload (a healthy N-rank run of
+    --full's four workloads takes a few minutes at most)"""
+    wl = WORKLOADS_FULL if "--full" in argv else WORKLOADS_PLAIN
     for k, a in enumerate(argv):
         if a == "--deadline" and k + 1 < len(argv):
             return float(argv[k + 1])
@@ -251,21 +268,60 @@ def gather_rank_stats(world, el, steps, stream_ms, ar_ms, n):
     """N > 1, every rank: each rank's wall step, kernel-stream step,
     all-reduce time and frames (all_gather over the control plane, gloo), and
     the max over ranks of the timed region's wall time, which `value` divides
-    by.  Returns (per_rank list, max wall seconds)."""
-    mine = torch.tensor([el / max(steps, 1) * 1e3, stream_ms, ar_ms, float(n)], dtype=torch.float64)
+    by.  ar_ms None (a plain run does not time the all-reduce alone) is None
+    in per_rank.  Returns (per_rank list, max wall seconds)."""
+    mine = torch.tensor([el / max(steps, 1) * 1e3, stream_ms,
+                         float("nan") if ar_ms is None else ar_ms, float(n)], dtype=torch.float64)
     allr = [torch.zeros_like(mine) for _ in range(world)]
     torch.distributed.all_gather(allr, mine)
     per_rank = [dict(rank=r, ms_per_step=round(float(x[0]), 4),
                      stream_ms_per_step=round(float(x[1]), 4),
-                     allreduce_ms=round(float(x[2]), 4), frames=int(x[3]))
+                     allreduce_ms=None if bool(torch.isnan(x[2])) else round(float(x[2]), 4),
+                     frames=int(x[3]))
                 for r, x in enumerate(allr)]
     t = torch.tensor([el], dtype=torch.float64)
     torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     return per_rank, float(t.item())
 
 
+DUMP_FRAMES = 1 << 18  # verdicts written by --dump-outputs (16 MiB as float32)
+DUMP_SEED = 0x0D0B
+
+
+def dump_outputs(d, out, n, counts):
+    """--dump-outputs DIR: what the last timed step left with its caller, as
+    float .npy files in DIR (under 32 MB in all, at cfg5's 1M flows):
+      verdicts.npy        float32 [m, 16]: the 16 verdict bytes (rxg_verdict,
+                          include/rxgpu.h) of m frames of the burst, one row
+                          per frame, each byte as a number (exact in float32);
+                          every frame when n <= DUMP_FRAMES, else a fixed
+                          seeded sample of DUMP_FRAMES frames in rising order;
+      verdict_frames.npy  float64 [m]: the index of each row's frame;
+      counts.npy          float64 [nflows]: the per-flow count vector after
+                          that step (UDP flows, then TCP; it accumulates over
+                          the warmup and timed steps; zeros with --no-counts).
+    The burst is a pure function of the workload (counter-based pktgen), so
+    two runs with the same arguments write the same files."""
+    os.makedirs(d, exist_ok=True)
+    if n > DUMP_FRAMES:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_FRAMES, replace=False))
+    else:
+        idx = np.arange(n)
+    idx = idx.astype(np.int64)
+    rows = out[:n * 16].view(n, 16).index_select(0, torch.from_numpy(idx).to(out.device))
+    np.save(os.path.join(d, "verdicts.npy"), rows.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(d, "verdict_frames.npy"), idx.astype(np.float64))
+    np.save(os.path.join(d, "counts.npy"), counts.cpu().numpy().astype(np.float64))
+    log(f"bench: outputs of the last step ({len(idx)} of {n} verdicts, {counts.numel()} counts) "
+        f"in {d}")
+
+
 def run_workload(name, ctx, rank, world, steps, warmup, dev, coll=None, parity_sample=4096,
-                 oracle_threads=1, shard_mode="direct"):
+                 oracle_threads=1, shard_mode="direct", full=True, dump_dir=None):
+    """one workload: setup, clock ramp, warmup, the timed steps, then the
+    outputs of the last step to dump_dir (if given).  full: also every leg
+    that takes runs or checks of its own (see the module docstring); without
+    it their fields are None"""
     w = rxdist.WORKLOADS[name]
     cfg = rxdist.gen_cfg(name)
     ul = w["unit_log2"]
@@ -376,47 +432,52 @@ def run_workload(name, ctx, rank, world, steps, warmup, dev, coll=None, parity_s
         torch.distributed.barrier()
     el = time.perf_counter() - t0
     kms = [ev[0].elapsed_time(ev[1]) / max(steps, 1)]
+    if dump_dir:
+        dump_outputs(dump_dir, out, n, counts)
     per_rank = None
     ar_ms = None
     if world > 1:
-        # the collective alone: `steps` count all-reduces back to back on the
-        # collective stream (HIP events on that stream), after the timed region
-        aev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        torch.distributed.barrier()
-        torch.cuda.synchronize(dev)
-        aev[0].record(cs)
-        for _ in range(steps):
-            coll(step_counts[0], cs)
-        aev[1].record(cs)
-        torch.cuda.synchronize(dev)
-        ar_ms = aev[0].elapsed_time(aev[1]) / max(steps, 1)
+        if full:
+            # the collective alone: `steps` count all-reduces back to back on the
+            # collective stream (HIP events on that stream), after the timed region
+            aev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            torch.distributed.barrier()
+            torch.cuda.synchronize(dev)
+            aev[0].record(cs)
+            for _ in range(steps):
+                coll(step_counts[0], cs)
+            aev[1].record(cs)
+            torch.cuda.synchronize(dev)
+            ar_ms = aev[0].elapsed_time(aev[1]) / max(steps, 1)
         per_rank, el = gather_rank_stats(world, el, steps, kms[0], ar_ms, n)
-    kdisp = kernel_dispatches(ctx, pk, off, ln, n, ul, w["len_hint"], out, counts, stream, csh,
-                              dev, alg_bytes, cs if use_cs else None)
-    # counts: every delivered verdict counted once per step, on every rank
-    # after the all-reduce (the global histogram)
-    v = out[:n * 16].view(n, 16)
-    n_ok = int((v[:, 11].view(torch.int8) == 0).sum().item())
-    total_steps = warmup + steps
-    counted = int(counts.sum().item())
-    n_ok_all = n_ok
-    if world > 1:
-        t = torch.tensor([n_ok], dtype=torch.int64)
-        torch.distributed.all_reduce(t)
-        n_ok_all = int(t.item())
-    expect = n_ok_all * total_steps if COUNTS else None
-    # the count vector flow by flow: (all-reduced) counts == total_steps x the
-    # sum over ranks of each rank's histogram of its own delivered verdicts
-    # (UDP flow k -> k, TCP flow k -> nu + k), exchanged over the control plane
-    counts_match = None
-    if COUNTS:
-        ok = v[:, 11].view(torch.int8) == 0
-        fid = v[:, 0:4].contiguous().view(torch.int32).flatten().to(torch.int64)
-        cidx = torch.where(v[:, 10] == R.CLS_UDP, fid, fid + len(udp))[ok]
-        hist = torch.bincount(cidx, minlength=nflows)[:nflows].cpu()
+    kdisp = rc0_frac = counts_ok = counts_match = None
+    if full:
+        kdisp = kernel_dispatches(ctx, pk, off, ln, n, ul, w["len_hint"], out, counts, stream,
+                                  csh, dev, alg_bytes, cs if use_cs else None)
+        # counts: every delivered verdict counted once per step, on every rank
+        # after the all-reduce (the global histogram)
+        v = out[:n * 16].view(n, 16)
+        n_ok = int((v[:, 11].view(torch.int8) == 0).sum().item())
+        rc0_frac = n_ok / max(n, 1)
+        total_steps = warmup + steps
+        counted = int(counts.sum().item())
+        n_ok_all = n_ok
         if world > 1:
-            torch.distributed.all_reduce(hist)
-        counts_match = bool(torch.equal(counts.cpu(), hist * total_steps))
+            t = torch.tensor([n_ok], dtype=torch.int64)
+            torch.distributed.all_reduce(t)
+            n_ok_all = int(t.item())
+        counts_ok = not COUNTS or counted == n_ok_all * total_steps
+        # the count vector flow by flow: (all-reduced) counts == total_steps x the
+        # sum over ranks of each rank's histogram of its own delivered verdicts
+        # (UDP flow k -> k, TCP flow k -> nu + k), exchanged over the control plane
+        if COUNTS:
+            ok = v[:, 11].view(torch.int8) == 0
+            fid = v[:, 0:4].contiguous().view(torch.int32).flatten().to(torch.int64)
+            cidx = torch.where(v[:, 10] == R.CLS_UDP, fid, fid + len(udp))[ok]
+            hist = torch.bincount(cidx, minlength=nflows)[:nflows].cpu()
+            if world > 1:
+                torch.distributed.all_reduce(hist)
+            counts_match = bool(torch.equal(counts.cpu(), hist * total_steps))
     kavg = float(np.mean(kms))
     n_all, alg_all = n, alg_bytes
     if world > 1:  # the whole job: frames and algorithmic bytes of every rank
@@ -429,14 +490,13 @@ def run_workload(name, ctx, rank, world, steps, warmup, dev, coll=None, parity_s
         gbps=alg_all * steps / el / 1e9, ms_per_step=el / steps * 1e3,
         kernel_ms_avg=kavg,
         alg_bytes_per_launch=alg_bytes, frame_bytes=frame_bytes,
-        rc0_frac=n_ok / max(n, 1), counts_ok=(expect is None or counted == expect),
-        counts_match=counts_match,
+        rc0_frac=rc0_frac, counts_ok=counts_ok, counts_match=counts_match,
         setup_s=round(t_setup, 2), count_stream=bool(COUNTS and csh is not None),
         ramp=ramp_info,
         shard_mode=shard_mode if world > 1 else None,
     )
     if world > 1:
-        res["allreduce_ms"] = round(ar_ms, 4)
+        res["allreduce_ms"] = round(ar_ms, 4) if ar_ms is not None else None
         res["allreduce_bytes"] = 8 * nflows
         res["per_rank"] = per_rank
     achieved = alg_bytes / (kavg * 1e-3) / 1e9  # this rank's kernel (HIP events)
@@ -444,6 +504,28 @@ def run_workload(name, ctx, rank, world, steps, warmup, dev, coll=None, parity_s
                            unit="GB/s", frac=round(achieved / HBM_PEAK_GBS, 4),
                            traffic=pmc_traffic(name) if world == 1 else None,
                            kernel=kdisp)
+    if full:
+        full_legs(res, name, ctx, rank, world, steps, warmup, dev, parity_sample, oracle_threads,
+                  shard_mode, w, udp, tcb, nflows, stream, csh, pk, off, ln, n, gidx, gcfg, ul,
+                  out, counts, frame_bytes, kdisp)
+    else:
+        res["parity"] = res["digest"] = None
+    if split_destroy is not None:
+        split_destroy()
+        res["cu_split"] = dict(count_cus=CU_SPLIT, note="count stream on CUs of its own, "
+                               "classify on the rest (hipExtStreamCreateWithCUMask)")
+    del pk, off, ln, out
+    torch.cuda.empty_cache()
+    return res
+
+
+def full_legs(res, name, ctx, rank, world, steps, warmup, dev, parity_sample, oracle_threads,
+              shard_mode, w, udp, tcb, nflows, stream, csh, pk, off, ln, n, gidx, gcfg, ul, out,
+              counts, frame_bytes, kdisp):
+    """--full, after a workload's timed steps and over the same burst: the
+    slot-shape ceiling, the oracle parity sample, the golden digests, the 8-B
+    verdict leg and the TX checksum leg, into res"""
+    sh = stream.cuda_stream
     g = w["gen"]
     if world == 1 and g.get("frame_len") and not g.get("packed") and not g.get("size_mode") \
             and g["slot_bytes"] <= 1536:
@@ -491,13 +573,6 @@ def run_workload(name, ctx, rank, world, steps, warmup, dev, coll=None, parity_s
                                gb_per_s=round(tx_bytes / tms / 1e6, 1),
                                frac=round(tx_bytes / tms / 1e6 / HBM_PEAK_GBS, 4),
                                traffic=pmc_traffic(name, "tx_cksum"))
-    if split_destroy is not None:
-        split_destroy()
-        res["cu_split"] = dict(count_cus=CU_SPLIT, note="count stream on CUs of its own, "
-                               "classify on the rest (hipExtStreamCreateWithCUMask)")
-    del pk, off, ln, out
-    torch.cuda.empty_cache()
-    return res
 
 
 KDISP = 20  # dispatches of the per-dispatch pass (roofline.kernel)
@@ -1686,8 +1761,18 @@ def main():
     # to a single host-side hiccup than 20 (4.6 ms)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--workload", default="cfg2,cfg3,cfg4,cfg5",
-                    help="BASELINE configs to run; the first is the headline line (cfg2 = configs[1])")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline's timed steps, everything else the benchmark "
+                         "measures and checks: the other workloads, per-dispatch roofline, oracle "
+                         "parity and golden digests, 8-B verdicts, TX checksum, CPU baselines, "
+                         "cfg1, socket-API rates, HBM read ceiling, the detail file (the --no-* "
+                         "options below take legs out of it)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write the headline workload's outputs of the "
+                         "last step to DIR as float .npy files (see dump_outputs)")
+    ap.add_argument("--workload", default="",
+                    help="BASELINE configs to run; the first is the headline line (cfg2 = "
+                         f"configs[1]); default {WORKLOADS_PLAIN}, with --full {WORKLOADS_FULL}")
     ap.add_argument("--no-cfg1", action="store_true",
                     help="skip BASELINE configs[0] (pcap, 1 flow; rank 0 at N = 1 only)")
     ap.add_argument("--cpu-budget", type=float, default=4.0,
@@ -1817,29 +1902,31 @@ def main():
         return
     cores = host_cores()
     oracle_threads = max(1, cores["threads"] // max(1, min(world, 8)))
-    names = [s.strip() for s in a.workload.split(",") if s.strip()]
+    wl = a.workload or (WORKLOADS_FULL if a.full else WORKLOADS_PLAIN)
+    names = [s.strip() for s in wl.split(",") if s.strip()]
     results = {}
-    for nm in names:
+    for i, nm in enumerate(names):
         stage(rank, f"{nm}: setup")
         coll = None
         if world > 1:
             u, t = R.gen_flows(rxdist.gen_cfg(nm))
             coll = collective_fn(group, nccl_group, len(u) + len(t))
         results[nm] = run_workload(nm, ctx, rank, world, a.steps, a.warmup, dev, coll,
-                                   a.parity_sample, oracle_threads, a.shard_gen)
+                                   a.parity_sample, oracle_threads, a.shard_gen, full=a.full,
+                                   dump_dir=a.dump_outputs if i == 0 and rank == 0 else None)
         log(nm, json.dumps({k: v for k, v in results[nm].items() if k != "desc"}))
     head = results[names[0]]
 
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu:
         for i, nm in enumerate(names):
             results[nm]["cpu_baseline"] = cpu_baseline(nm, a.cpu_budget if i == 0
                                                        else a.cpu_budget / 2, cores)
     cfg1 = None
-    if rank == 0 and world == 1 and not a.no_cfg1:
+    if a.full and rank == 0 and world == 1 and not a.no_cfg1:
         cfg1 = run_cfg1(local, dev, a.steps, a.warmup, 0 if a.no_cpu else a.cpu_budget / 2, cores)
         log("cfg1", json.dumps(cfg1))
     sock = {}
-    if rank == 0 and world == 1 and not a.no_sockrate:
+    if a.full and rank == 0 and world == 1 and not a.no_sockrate:
         for nm in ("cfg2", "cfg3"):
             try:
                 sock[nm] = socket_api(local, nm, 0 if a.no_cpu else a.cpu_budget / 2, cores,
@@ -1848,7 +1935,7 @@ def main():
             except Exception as e:  # reported in the line, never silent
                 sock[nm] = dict(error=repr(e))
                 log(f"socket_api {nm} failed: {e!r}")
-    ceiling = hbm_read_ceiling(local) if rank == 0 and world == 1 else None
+    ceiling = hbm_read_ceiling(local) if a.full and rank == 0 and world == 1 else None
 
     if a.e2e and rank == 0:
         pk = pcie_peaks(local)
@@ -1859,19 +1946,22 @@ def main():
             log("e2e", json.dumps(r))
             results[nm]["e2e_pcie"] = r
 
-    parity_bad = sum(r["parity"]["mismatches"] for r in results.values()) + \
+    # (a plain run checks nothing: its parity and digest are None)
+    parity_bad = sum(r["parity"]["mismatches"] for r in results.values() if r["parity"]) + \
         sum(r["counts_match"] is False for r in results.values()) + \
         (cfg1["parity"]["mismatches"] if cfg1 else 0) + \
-        sum(r["digest"]["digest_ok"] is False for r in results.values()) + \
+        sum(r["digest"]["digest_ok"] is False for r in results.values() if r["digest"]) + \
         sum(("verdict8" in r and (not r["verdict8"]["equals_projection"]
                                   or r["verdict8"]["digest_ok"] is False)) for r in results.values())
     if rank == 0:
         line = build_line(names, results, a.steps, a.warmup, a.ramp_ms, world, ndev, collective,
                           rccl_nranks, ceiling, cfg1, sock)
         # stdout: the compact line (the driver parses a bounded tail of
-        # stdout); every measured detail goes to the detail file
-        path = write_detail(line)
+        # stdout); with --full every measured detail goes to the detail file
+        # (a plain run writes it only where BENCH_DETAIL names a path)
+        path = write_detail(line) if a.full or os.environ.get("BENCH_DETAIL") else None
         short = compact_line(line)
+        short["full"] = bool(a.full)
         short["detail"] = os.path.relpath(path, ROOT) if path else None
         print(json.dumps(short, separators=(",", ":")), file=JSON_OUT, flush=True)
     ctx.close()

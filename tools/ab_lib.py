@@ -19,7 +19,7 @@ for r in range(rounds):
         env = dict(os.environ)
         if lib:
             env["RXGPU_LIB"] = lib
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", wls, "--no-cpu",
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", wls, "--no-cpu",
                "--no-cfg1", "--no-sockrate", "--no-tx", "--no-v8", "--parity-sample", "256", "--steps", "50"]
         p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
         if p.returncode != 0:

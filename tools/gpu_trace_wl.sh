@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out; mkdir -p $OUT
 export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/tr_${WL} -o run \
-    -- python3 bench.py --workload ${WL} --no-cpu --no-cfg1 --no-tx --steps 10 --warmup 3 ${ARGS:-} \
+    -- python3 bench.py --full --workload ${WL} --no-cpu --no-cfg1 --no-tx --steps 10 --warmup 3 ${ARGS:-} \
     > $OUT/tr_${WL}.log 2>&1 || { tail -20 $OUT/tr_${WL}.log; exit 1; }
 f=$(find $OUT/tr_${WL} -name '*kernel_trace.csv' | head -1)
 python3 - "$f" > $OUT/trace_${WL}.txt <<'PY'

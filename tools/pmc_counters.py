@@ -24,7 +24,7 @@ def main():
         d = os.path.join(ROOT, "gpurun_out", f"pmcx_{tag}_{wl}_{i}")
         cmd = ["rocprofv3", "--pmc", *group.split(), "--output-format", "csv", "-d", d, "-o", "run",
                "--", sys.executable, os.path.join(ROOT, "bench.py"), "--workload", wl, "--steps",
-               "3", "--warmup", "1", "--no-cpu", *extra]
+               "3", "--warmup", "1", "--full", "--no-cpu", *extra]
         r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, TMPDIR="/tmp"),
                            capture_output=True, text=True, timeout=600)
         if r.returncode != 0:

@@ -22,7 +22,7 @@ def collect(workload, variant, outdir):
     cmd = ["rocprofv3", "--pmc", *COUNTERS, "--output-format", "csv", "-d", d, "-o", "run", "--",
            sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--steps", "3",
            "--warmup", "1", "--no-cpu", "--no-cfg1", "--no-sockrate", "--no-tx", "--no-v8",
-           "--parity-sample", "0", "--variant", variant]
+           "--parity-sample", "0", "--variant", variant, "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, TMPDIR="/tmp"), capture_output=True,
                        text=True, timeout=240)
     # the ablation's verdicts are wrong by construction: bench.py exits 3 on them

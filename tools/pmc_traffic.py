@@ -3,7 +3,7 @@
 
 Two separate counter passes (TCC has 4 slots: FETCH_SIZE needs 3, WRITE_SIZE
 2 — MI355X_MICROARCH.md §rocprofv3 PMC slots), each with nothing but the
-counter collection, over `bench.py --workload <w> --no-cpu`.  Per dispatch of
+counter collection, over `bench.py --full --workload <w> --no-cpu`.  Per dispatch of
 rx_classify_kernel (and of K2 tx_cksum_kernel, the bench's TX leg): hbm_bytes = 2 * FETCH_SIZE * 1024 + WRITE_SIZE * 1024
 (gfx950 correction: FETCH_SIZE reports half the bytes of a wide coalesced
 streaming read, MI355X_MICROARCH.md §HBM; WRITE_SIZE is exact for 16-B
@@ -24,7 +24,8 @@ def collect(workload, counter, outdir, variant=""):
     d = os.path.join(outdir, f"pmc_{workload}_{counter}{'_' + variant.replace(',', '-') if variant else ''}")
     cmd = ["rocprofv3", "--pmc", counter, "--output-format", "csv", "-d", d, "-o", "run", "--",
            sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--steps", "3",
-           "--warmup", "1", "--no-cpu", "--no-cfg1", "--no-sockrate", "--no-v8", "--parity-sample", "0"]
+           "--warmup", "1", "--full", "--no-cpu", "--no-cfg1", "--no-sockrate", "--no-v8",
+           "--parity-sample", "0"]
     if variant:  # a forced kernel variant (tuning comparisons)
         cmd += ["--variant", variant]
     env = dict(os.environ, TMPDIR="/tmp")
