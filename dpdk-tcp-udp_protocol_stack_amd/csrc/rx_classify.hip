@@ -1,7 +1,8 @@
 // rx_classify.hip — K1: fused parse + L4 checksum + flow classify (gfx950).
 //
-// Three kernel shapes, picked per typical frame length by rx_pick_variant
-// (bottom of this file); every shape is correct for any layout and length:
+// Five kernel shapes; rx_pick_variant (bottom of this file) picks among the
+// first four per typical frame length, and every shape is correct for any
+// layout and length:
 //   lane kernel   (rx_classify_lane_kernel)   one frame per lane: 64-B frames
 //                 (heads staged through LDS by coalesced 1-KiB wave loads,
 //                 two tiles' bytes (a grid stride apart) issued per trip,
@@ -9,8 +10,17 @@
 //   group kernel  (rx_classify_kernel)        G lanes per frame: 1500-B frames
 //                 (described below);
 //   stream kernel (rx_classify_stream_kernel) heads per thread, tails streamed
-//                 by the block as one contiguous span with prefix sums: mixed
-//                 sizes (IMIX) and jumbo frames.
+//                 by the block as one contiguous span with prefix sums: jumbo
+//                 frames;
+//   SH kernel     (rx_classify_sh_kernel)     the stream kernel with the heads
+//                 taken out of the block stream: mixed sizes (IMIX);
+//   WC kernel     (rx_classify_wc_kernel)     a wave owns consecutive frames
+//                 and reads their span contiguously (RX_DIAG build only).
+// Beside them: rx_bin_kernel splits a mixed burst into a small and a large
+// index list for the lane and group kernels (the binned path, pipe 20), and
+// the count kernels (rx_count_slab_kernel, rx_count_reduce_kernel,
+// rx_count_reduce_few_kernel) sum the per-frame count indices when the flows
+// are too many for a per-block LDS histogram.
 // The variant table (k_variants) holds the defaults and a few measured
 // alternatives; tuning shapes and diagnostic ablations (wrong verdicts by
 // construction) compile only into the RX_DIAG build (librxgpu_diag.so).
@@ -104,8 +114,8 @@ __device__ __forceinline__ uint64_t verdict8_of(uint4 v) {
                         ((v.w & 1u) << 30) | ((v.w & 0x100u) << 23);
     return (uint64_t)v.x | ((uint64_t)hi << 32);
 }
-// WT: write-through (sc1) stores; PLAIN: ordinary stores; else non-temporal
-template <bool WT = false, bool PLAIN = false>
+// WT: write-through (sc1) stores; else non-temporal
+template <bool WT = false>
 __device__ __forceinline__ void st_verdict(const rx_ft_dev &ft, uint4 *__restrict__ out, uint64_t p,
                                            uint4 v) {
     if constexpr (RX_V8) {
@@ -113,14 +123,10 @@ __device__ __forceinline__ void st_verdict(const rx_ft_dev &ft, uint4 *__restric
         const uint64_t w = verdict8_of(v);
         if constexpr (WT)
             asm volatile("global_store_dwordx2 %0, %1, off sc1" ::"v"(o), "v"(w) : "memory");
-        else if constexpr (PLAIN)
-            *o = w;
         else
             __builtin_nontemporal_store(w, o);
     } else if constexpr (WT) {
         stg16_wt(&out[p], v);
-    } else if constexpr (PLAIN) {
-        out[p] = v;
     } else {
         stg16(&out[p], v);
     }
@@ -154,7 +160,7 @@ __device__ __forceinline__ void group_desc(group_frames<FPG, P> &S, uint64_t til
     }
 }
 
-template <int G, int FPG, int P, bool NTL = true>
+template <int G, int FPG, int P>
 __device__ __forceinline__ void group_load(group_frames<FPG, P> &S, int32_t s0) {
 #pragma unroll
     for (int f = 0; f < FPG; ++f)
@@ -162,7 +168,7 @@ __device__ __forceinline__ void group_load(group_frames<FPG, P> &S, int32_t s0) 
         for (int q = 0; q < P; ++q) {
             const int32_t s = s0 + q * 16 * G;
             S.c[f][q] = make_uint4(0, 0, 0, 0);
-            if (s < S.cap[f]) S.c[f][q] = ldg16<NTL>(S.fb[f] + s);
+            if (s < S.cap[f]) S.c[f][q] = ldg16<true>(S.fb[f] + s);
         }
 }
 
@@ -173,7 +179,7 @@ __device__ __forceinline__ void group_load(group_frames<FPG, P> &S, int32_t s0) 
 // loads of a lane in flight; a pass past a frame's end loads the frame's first
 // chunk again, an L1/L2 hit, and adds nothing), which keeps enough bytes in
 // flight for jumbo frames.
-template <int G, int P, int FPG, bool NTL = true, int RI = 0, bool WT = false, bool H16 = false>
+template <int G, int P, int FPG, int RI = 0, bool WT = false, bool H16 = false>
 __device__ __forceinline__ void group_process(group_frames<FPG, P> &S, uint32_t gl, uint32_t gbase,
                                               int32_t s0, const rx_ft_dev &ft,
                                               uint4 *__restrict__ out,
@@ -302,7 +308,7 @@ __device__ __forceinline__ void group_process(group_frames<FPG, P> &S, uint32_t 
 #pragma unroll
                 for (int u = 0; u < RI; ++u) { // unconditional: partial wait counts
                     const int32_t s = s0 + sb + u * STEP;
-                    r[f][u] = ldg16<NTL>(S.fb[f] + (s < ends[f] ? s : 0));
+                    r[f][u] = ldg16<true>(S.fb[f] + (s < ends[f] ? s : 0));
                 }
 #pragma unroll
             for (int f = 0; f < FPG; ++f)
@@ -448,8 +454,8 @@ __device__ __forceinline__ void group_process(group_frames<FPG, P> &S, uint32_t 
 // (tools/membw_cfg3, profiles/r06c, r06d).
 // H16: the per-block LDS histogram in 16-bit bin pairs (half the LDS; the
 // launch uses it only when no block classifies 65536 frames or more)
-template <int G, int P, int FPG, int PIPE, bool NTL = true, int RI = 0, int MINW = 1, bool WT = false,
-          int WB = 0, bool H16 = false>
+template <int G, int P, int FPG, int PIPE, int RI = 0, int MINW = 1, bool WT = false, int WB = 0,
+          bool H16 = false>
 __global__ __launch_bounds__(256, MINW) void rx_classify_kernel(
     const uint8_t *__restrict__ pkts, const uint32_t *__restrict__ off,
     const uint16_t *__restrict__ len, uint32_t n, uint32_t unit_log2, rx_ft_dev ft,
@@ -496,16 +502,16 @@ __global__ __launch_bounds__(256, MINW) void rx_classify_kernel(
             group_frames<FPG, P> A;
             if (t0 < t1) {
                 group_desc<G>(A, t0, n, grp, pkts, off, len, unit_log2);
-                group_load<G, FPG, P, NTL>(A, s0);
+                group_load<G, FPG, P>(A, s0);
             }
             uint32_t k = 0;
             uint64_t first = t0;
             for (uint64_t tile = t0; tile < t1; ++tile) { // block-uniform trips
-                group_process<G, P, FPG, NTL, RI, WT, H16>(A, gl, gbase, s0, ft, out, counts, hist,
+                group_process<G, P, FPG, RI, WT, H16>(A, gl, gbase, s0, ft, out, counts, hist,
                                                            lds_bins, vb + k * TILE);
                 if (tile + 1 < t1) { // the next tile's loads go out before the batch is written
                     group_desc<G>(A, tile + 1, n, grp, pkts, off, len, unit_log2);
-                    group_load<G, FPG, P, NTL>(A, s0);
+                    group_load<G, FPG, P>(A, s0);
                 }
                 if (++k == (uint32_t)WB || tile + 1 == t1) {
                     __syncthreads();
@@ -530,22 +536,22 @@ __global__ __launch_bounds__(256, MINW) void rx_classify_kernel(
     group_frames<FPG, P> A;
     if (tile * TILE < n) {
         group_desc<G>(A, tile, n, grp, pkts, off, len, unit_log2, idx);
-        group_load<G, FPG, P, NTL>(A, s0);
+        group_load<G, FPG, P>(A, s0);
     }
     if constexpr (PIPE) {
         group_frames<FPG, P> B;
         group_desc<G>(B, tile + gridDim.x, n, grp, pkts, off, len, unit_log2, idx);
         for (; tile * TILE < n; tile += gridDim.x) {
-            group_load<G, FPG, P, NTL>(B, s0); // no-op lanes past the end (cap 0)
-            group_process<G, P, FPG, NTL, RI, WT, H16>(A, gl, gbase, s0, ft, out, counts, hist, lds_bins);
+            group_load<G, FPG, P>(B, s0); // no-op lanes past the end (cap 0)
+            group_process<G, P, FPG, RI, WT, H16>(A, gl, gbase, s0, ft, out, counts, hist, lds_bins);
             A = B;
             group_desc<G>(B, tile + 2 * (uint64_t)gridDim.x, n, grp, pkts, off, len, unit_log2, idx);
         }
     } else {
         for (; tile * TILE < n; tile += gridDim.x) {
-            group_process<G, P, FPG, NTL, RI, WT, H16>(A, gl, gbase, s0, ft, out, counts, hist, lds_bins);
+            group_process<G, P, FPG, RI, WT, H16>(A, gl, gbase, s0, ft, out, counts, hist, lds_bins);
             group_desc<G>(A, tile + gridDim.x, n, grp, pkts, off, len, unit_log2, idx);
-            group_load<G, FPG, P, NTL>(A, s0);
+            group_load<G, FPG, P>(A, s0);
         }
     }
 
@@ -555,8 +561,8 @@ __global__ __launch_bounds__(256, MINW) void rx_classify_kernel(
     }
 }
 
-template <int G, int P, int FPG, int PIPE = 0, bool NTL = true, int RI = 0, int MINW = 1,
-          bool WT = false, int WB = 0, bool H16 = false>
+template <int G, int P, int FPG, int PIPE = 0, int RI = 0, int MINW = 1, bool WT = false,
+          int WB = 0, bool H16 = false>
 hipError_t launch_v(const uint8_t *pkts, const uint32_t *off, const uint16_t *len, uint32_t n,
                     uint32_t unit_log2, const rx_ft_dev &ft, uint4 *out, unsigned long long *counts,
                     uint32_t lds_bins, hipStream_t s, const uint32_t *idx = nullptr,
@@ -568,7 +574,7 @@ hipError_t launch_v(const uint8_t *pkts, const uint32_t *off, const uint16_t *le
     // resident blocks: one wave of blocks, equal shares, no tail
     int cu = 0, bpc = 0;
     hipError_t e = rx_occupancy(
-        reinterpret_cast<const void *>(rx_classify_kernel<G, P, FPG, PIPE, NTL, RI, MINW, WT, WB, H16>), 256,
+        reinterpret_cast<const void *>(rx_classify_kernel<G, P, FPG, PIPE, RI, MINW, WT, WB, H16>), 256,
         lds, &cu, &bpc);
     if (e != hipSuccess) return e;
     const uint64_t tiles = ((uint64_t)n + TILE - 1) / TILE;
@@ -582,10 +588,10 @@ hipError_t launch_v(const uint8_t *pkts, const uint32_t *off, const uint16_t *le
         // (index-list mode: n_dev may shorten it, never lengthen) stays below
         // that, else the 32-bit histogram
         if (lds_bins && ((tiles + blocks - 1) / blocks) * TILE > 65535u)
-            return launch_v<G, P, FPG, PIPE, NTL, RI, MINW, WT, WB, false>(
+            return launch_v<G, P, FPG, PIPE, RI, MINW, WT, WB, false>(
                 pkts, off, len, n, unit_log2, ft, out, counts, lds_bins, s, idx, n_dev);
     }
-    hipLaunchKernelGGL((rx_classify_kernel<G, P, FPG, PIPE, NTL, RI, MINW, WT, WB, H16>), dim3((uint32_t)blocks), dim3(256), lds, s,
+    hipLaunchKernelGGL((rx_classify_kernel<G, P, FPG, PIPE, RI, MINW, WT, WB, H16>), dim3((uint32_t)blocks), dim3(256), lds, s,
                        pkts, off, len, n, unit_log2, ft, out, counts, lds_bins, idx, n_dev);
     return hipGetLastError();
 }
@@ -704,16 +710,13 @@ __device__ __forceinline__ void lane_stage(lane_frame &L, const uint4 (&v)[4], b
     __builtin_amdgcn_wave_barrier();
 }
 
-// Parse + checksum + probe + verdict of one lane-owned frame.  `next` (may be
-// null) is the following trip's frame: its loads are issued here, after the
-// current frame's arithmetic and before the current frame's bucket probe, so
-// the bulk bytes of trip t+1 are in flight across the probe latency of trip t.
+// Parse + checksum + probe + verdict of one lane-owned frame (everything but
+// the store): returns the 16-B verdict and the per-flow count slot (~0u = not
+// counted).
 // ABL (diagnostic builds only, never selected automatically): 1 = no bucket
 // probe, 4 = no verdict store, 8 = no checksum arithmetic.
-// Verdict of one lane-owned frame (everything but the store): returns the
-// 16-B verdict and the per-flow count slot (~0u = not counted).
 template <int ABL = 0, bool NTL = true, bool LDT = false>
-__device__ __forceinline__ uint4 lane_verdict(lane_frame &L, lane_frame *next, const rx_ft_dev &ft,
+__device__ __forceinline__ uint4 lane_verdict(lane_frame &L, const rx_ft_dev &ft,
                                               uint32_t *count_idx, const uint2 *lt = nullptr,
                                               const uint16_t *lw = nullptr) {
     const int32_t cp = L.cap;
@@ -789,8 +792,6 @@ __device__ __forceinline__ uint4 lane_verdict(lane_frame &L, lane_frame *next, c
     }
     const uint32_t stored = is_udp ? (c2.z & 0xFFFFu) : (is_tcp ? (c3.x >> 16) : 0u);
     const bool ok = l4 && stored == ck;
-
-    if (next) lane_load<NTL>(*next); // trip t+1 bytes in flight from here on
 
     // flow probe: the whole 64-B bucket per lane
     uint32_t flow = RXG_FLOW_NONE;
@@ -991,15 +992,8 @@ __device__ __forceinline__ void put_count_idx_wave(const rx_ft_dev &ft, uint64_t
     }
 }
 
-template <bool ST_NT>
-__device__ __forceinline__ void lane_store(const rx_ft_dev &ft, uint4 *__restrict__ out, uint64_t p,
-                                           uint4 v) {
-    st_verdict<false, !ST_NT>(ft, out, p, v);
-}
-
-// the original one-shot form: verdict, store, count
 // the store and count half of lane_process (PIPE 23 defers it to the trip's end)
-template <int ABL = 0, bool ST_NT = true>
+template <int ABL = 0>
 __device__ __forceinline__ void lane_finish(const lane_frame &L, uint4 v, uint32_t idx,
                                             const rx_ft_dev &ft, uint4 *__restrict__ out,
                                             unsigned long long *__restrict__ counts, uint32_t *hist,
@@ -1008,52 +1002,51 @@ __device__ __forceinline__ void lane_finish(const lane_frame &L, uint4 v, uint32
         if (ABL & 4)
             asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
         else
-            lane_store<ST_NT>(ft, out, L.p, v);
+            st_verdict(ft, out, L.p, v);
         lane_count(idx, counts, hist, lds_bins);
         if (ft.count_idx) put_count_idx(ft, L.p, idx);
     }
 }
 
 // LEAN (PIPE 16): lane_verdict_fast first, lane_verdict for the waves it declines
-template <int ABL = 0, bool ST_NT = true, bool NTL = true, bool LDT = false, bool LEAN = false>
-__device__ __forceinline__ void lane_process(lane_frame &L, lane_frame *next,
-                                             const rx_ft_dev &ft, uint4 *__restrict__ out,
+template <int ABL = 0, bool NTL = true, bool LDT = false, bool LEAN = false>
+__device__ __forceinline__ void lane_process(lane_frame &L, const rx_ft_dev &ft,
+                                             uint4 *__restrict__ out,
                                              unsigned long long *__restrict__ counts,
                                              uint32_t *hist, uint32_t lds_bins,
                                              const uint2 *lt = nullptr, const uint16_t *lw = nullptr) {
     uint32_t idx;
     uint4 v;
     if (!(LEAN && LDT && (ABL & ~4) == 0 && lane_verdict_fast(L, ft, &v, &idx, lw)))
-        v = lane_verdict<ABL, NTL, LDT>(L, next, ft, &idx, lt, lw);
+        v = lane_verdict<ABL, NTL, LDT>(L, ft, &idx, lt, lw);
     if (L.valid) {
         if (ABL & 4)
             asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
         else
-            lane_store<ST_NT>(ft, out, L.p, v);
+            st_verdict(ft, out, L.p, v);
         lane_count(idx, counts, hist, lds_bins);
         if (ft.count_idx) put_count_idx(ft, L.p, idx);
     }
 }
 
-// PIPE = 0: load, process, repeat.  PIPE = 1: trip t+1's descriptors are
-// fetched at the top of trip t and its frame bytes are issued mid-trip.
-// PIPE = 2: as 1, register budget capped for 6 waves per SIMD.  PIPE = 3:
-// only the descriptors are prefetched (frame bytes loaded at the top).
-// LDT: the compact UDP table (ft.udpc) is copied into LDS after the histogram
-// and UDP frames probe it there (PIPE 0 only)
-template <int PIPE, int ABL = 0, bool ST_NT = true, bool NTL = true, bool LDT = false>
-__global__ __launch_bounds__(256, PIPE == 2 ? 6 : 1) void rx_classify_lane_kernel(
+// PIPE = 0: load, process, repeat; 12 / 14 / 16 / 18 / 19 / 21-25: the staged
+// and software-pipelined forms described at their branches below.
+// NTL: non-temporal frame loads (lane_load and lane_verdict's remainder loop).
+// LDT: the compact UDP table (ft.udpc) and the port window (ft.udpw) are
+// copied into LDS after the histogram and UDP frames probe them there
+template <int PIPE, int ABL = 0, bool NTL = true, bool LDT = false>
+__global__ __launch_bounds__(256) void rx_classify_lane_kernel(
     const uint8_t *__restrict__ pkts, const uint32_t *__restrict__ off,
     const uint16_t *__restrict__ len, uint32_t n, uint32_t unit_log2, rx_ft_dev ft,
     uint4 *__restrict__ out, unsigned long long *__restrict__ counts, uint32_t lds_bins,
     const uint32_t *__restrict__ idx, const uint32_t *__restrict__ n_dev) {
-    static_assert(!LDT || PIPE == 0 || PIPE == 12 || PIPE == 14 || PIPE == 16 || PIPE == 18 ||
+    static_assert(PIPE == 0 || PIPE == 12 || PIPE == 14 || PIPE == 16 || PIPE == 18 ||
                       PIPE == 19 || (PIPE >= 21 && PIPE <= 25),
-                  "LDS table: PIPE 0 / 12 / 14 / 16 / 18 / 19 / 21-25 only");
+                  "PIPE 0 / 12 / 14 / 16 / 18 / 19 / 21-25 only");
     constexpr bool LEAN = PIPE == 16 || PIPE == 18; // with lane_verdict_fast
     extern __shared__ __attribute__((aligned(16))) uint32_t hist[];
     uint2 *lt = reinterpret_cast<uint2 *>(hist + ((lds_bins + 3u) & ~3u));
-    // the port window after the compact table, then (PIPE 12/14/15) the stage
+    // the port window after the compact table, then (PIPE >= 12) the stage
     uint16_t *lw = reinterpret_cast<uint16_t *>(lt + (LDT ? ft.udpc_mask + 1u : 0u));
     const uint32_t lw_words = LDT ? ((ft.udpw_n + 7u) & ~7u) / 2u : 0u; // 16-B multiple
     if (n_dev) n = min(n, *n_dev); // index-list mode: the list length lives on the device
@@ -1070,43 +1063,12 @@ __global__ __launch_bounds__(256, PIPE == 2 ? 6 : 1) void rx_classify_lane_kerne
     if (LDT || lds_bins) __syncthreads();
     const uint64_t stride = (uint64_t)gridDim.x * 256;
     uint64_t p = (uint64_t)blockIdx.x * 256 + tid;
-    if constexpr (PIPE == 9) {
-        // issue order per trip t: frame(t) loads, descriptors(t+1), the
-        // deferred verdict store of t-1, then wait for frame(t) only.  The
-        // store ack and descriptor latency overlap the frame latency; the
-        // probe loop's waits drain everything before the next trip.
-        uint64_t base = (uint64_t)blockIdx.x * 256;
-        lane_frame L;
-        if (base < n) lane_desc(L, p, n, pkts, off, len, unit_log2);
-        uint4 pend = make_uint4(0, 0, 0, 0);
-        uint64_t pend_p = 0;
-        bool pend_valid = false;
-        for (; base < n; base += stride, p += stride) {
-            lane_load<NTL>(L);
-            const uint64_t np = p + stride;
-            const bool nvalid = np < n;
-            const uint64_t nq = nvalid ? np : 0;
-            const uint32_t noff = off[nq];
-            const uint16_t nlen = len[nq];
-            if (pend_valid) lane_store<ST_NT>(ft, out, pend_p, pend);
-            uint32_t idx;
-            pend = lane_verdict<ABL, NTL>(L, nullptr, ft, &idx);
-            pend_p = L.p;
-            pend_valid = L.valid;
-            lane_count(idx, counts, hist, lds_bins);
-            if (ft.count_idx && L.valid) put_count_idx(ft, L.p, idx);
-            L.p = np;
-            L.valid = nvalid;
-            L.fb = pkts + ((uint64_t)noff << unit_log2);
-            L.cap = nvalid ? (int32_t)nlen : 0;
-        }
-        if (pend_valid) lane_store<ST_NT>(ft, out, pend_p, pend);
-    } else if constexpr (PIPE == 0) {
+    if constexpr (PIPE == 0) {
         for (uint64_t base = (uint64_t)blockIdx.x * 256; base < n; base += stride, p += stride) {
             lane_frame L;
             lane_desc(L, p, n, pkts, off, len, unit_log2, idx);
             lane_load<NTL>(L);
-            lane_process<ABL, ST_NT, NTL, LDT>(L, nullptr, ft, out, counts, hist, lds_bins, lt, lw);
+            lane_process<ABL, NTL, LDT>(L, ft, out, counts, hist, lds_bins, lt, lw);
         }
     } else if constexpr (PIPE == 12) {
         // as 0, but a wave whose 64 frames fill consecutive 64-B slots loads
@@ -1128,7 +1090,7 @@ __global__ __launch_bounds__(256, PIPE == 2 ? 6 : 1) void rx_classify_lane_kerne
                 lane_load_staged(L, pkts + f0, stage, lane);
             else
                 lane_load<NTL>(L);
-            lane_process<ABL, ST_NT, NTL, LDT>(L, nullptr, ft, out, counts, hist, lds_bins, lt, lw);
+            lane_process<ABL, NTL, LDT>(L, ft, out, counts, hist, lds_bins, lt, lw);
         }
     } else if constexpr (PIPE == 14 || PIPE == 16) {
         // 12, software-pipelined: descriptors two trips ahead, frame bytes one
@@ -1158,7 +1120,7 @@ __global__ __launch_bounds__(256, PIPE == 2 ? 6 : 1) void rx_classify_lane_kerne
                 lane_desc_nb(D, p + 2 * stride, n, pkts, off, len, unit_log2);
                 cb = lane_issue(B, pkts, lane, vb);
                 lane_stage(A, va, ca, stage, lane);
-                lane_process<ABL, ST_NT, NTL, LDT, LEAN>(A, nullptr, ft, out, counts, hist, lds_bins, lt, lw);
+                lane_process<ABL, NTL, LDT, LEAN>(A, ft, out, counts, hist, lds_bins, lt, lw);
                 base += stride;
                 p += stride;
                 if (base >= n) break;
@@ -1166,7 +1128,7 @@ __global__ __launch_bounds__(256, PIPE == 2 ? 6 : 1) void rx_classify_lane_kerne
                 lane_desc_nb(A, p + 2 * stride, n, pkts, off, len, unit_log2);
                 ca = lane_issue(D, pkts, lane, va);
                 lane_stage(B, vb, cb, stage, lane);
-                lane_process<ABL, ST_NT, NTL, LDT, LEAN>(B, nullptr, ft, out, counts, hist, lds_bins, lt, lw);
+                lane_process<ABL, NTL, LDT, LEAN>(B, ft, out, counts, hist, lds_bins, lt, lw);
                 base += stride;
                 p += stride;
                 if (base >= n) break;
@@ -1174,7 +1136,7 @@ __global__ __launch_bounds__(256, PIPE == 2 ? 6 : 1) void rx_classify_lane_kerne
                 lane_desc_nb(B, p + 2 * stride, n, pkts, off, len, unit_log2);
                 cb = lane_issue(A, pkts, lane, vb);
                 lane_stage(D, va, ca, stage, lane);
-                lane_process<ABL, ST_NT, NTL, LDT, LEAN>(D, nullptr, ft, out, counts, hist, lds_bins, lt, lw);
+                lane_process<ABL, NTL, LDT, LEAN>(D, ft, out, counts, hist, lds_bins, lt, lw);
                 base += stride;
                 p += stride;
                 if (base >= n) break;
@@ -1182,7 +1144,7 @@ __global__ __launch_bounds__(256, PIPE == 2 ? 6 : 1) void rx_classify_lane_kerne
                 lane_desc_nb(D, p + 2 * stride, n, pkts, off, len, unit_log2);
                 ca = lane_issue(B, pkts, lane, va);
                 lane_stage(A, vb, cb, stage, lane);
-                lane_process<ABL, ST_NT, NTL, LDT, LEAN>(A, nullptr, ft, out, counts, hist, lds_bins, lt, lw);
+                lane_process<ABL, NTL, LDT, LEAN>(A, ft, out, counts, hist, lds_bins, lt, lw);
                 base += stride;
                 p += stride;
                 if (base >= n) break;
@@ -1190,7 +1152,7 @@ __global__ __launch_bounds__(256, PIPE == 2 ? 6 : 1) void rx_classify_lane_kerne
                 lane_desc_nb(A, p + 2 * stride, n, pkts, off, len, unit_log2);
                 cb = lane_issue(D, pkts, lane, vb);
                 lane_stage(B, va, ca, stage, lane);
-                lane_process<ABL, ST_NT, NTL, LDT, LEAN>(B, nullptr, ft, out, counts, hist, lds_bins, lt, lw);
+                lane_process<ABL, NTL, LDT, LEAN>(B, ft, out, counts, hist, lds_bins, lt, lw);
                 base += stride;
                 p += stride;
                 if (base >= n) break;
@@ -1198,7 +1160,7 @@ __global__ __launch_bounds__(256, PIPE == 2 ? 6 : 1) void rx_classify_lane_kerne
                 lane_desc_nb(B, p + 2 * stride, n, pkts, off, len, unit_log2);
                 ca = lane_issue(A, pkts, lane, va);
                 lane_stage(D, vb, cb, stage, lane);
-                lane_process<ABL, ST_NT, NTL, LDT, LEAN>(D, nullptr, ft, out, counts, hist, lds_bins, lt, lw);
+                lane_process<ABL, NTL, LDT, LEAN>(D, ft, out, counts, hist, lds_bins, lt, lw);
                 base += stride;
                 p += stride;
                 if (base >= n) break;
@@ -1255,16 +1217,16 @@ __global__ __launch_bounds__(256, PIPE == 2 ? 6 : 1) void rx_classify_lane_kerne
 #pragma unroll
                     for (int u = 0; u < T; ++u) {
                         lane_stage(X[u], v[u], c[u], stage, lane);
-                        vd[u] = lane_verdict<ABL, NTL, LDT>(X[u], nullptr, ft, &ix[u], lt, lw);
+                        vd[u] = lane_verdict<ABL, NTL, LDT>(X[u], ft, &ix[u], lt, lw);
                     }
 #pragma unroll
                     for (int u = 0; u < T; ++u)
-                        lane_finish<ABL, ST_NT>(X[u], vd[u], ix[u], ft, out, counts, hist, lds_bins);
+                        lane_finish<ABL>(X[u], vd[u], ix[u], ft, out, counts, hist, lds_bins);
                 } else {
 #pragma unroll
                     for (int u = 0; u < T; ++u) {
                         lane_stage(X[u], v[u], c[u], stage, lane);
-                        lane_process<ABL, ST_NT, NTL, LDT, LEAN>(X[u], nullptr, ft, out, counts, hist, lds_bins, lt, lw);
+                        lane_process<ABL, NTL, LDT, LEAN>(X[u], ft, out, counts, hist, lds_bins, lt, lw);
                     }
                 }
             };
@@ -1283,51 +1245,6 @@ __global__ __launch_bounds__(256, PIPE == 2 ? 6 : 1) void rx_classify_lane_kerne
                 for (int u = 0; u < T; ++u) asm volatile("" ::"v"(A[u].cap), "v"(A[u].fb));
             }
         }
-    } else if constexpr (PIPE == 3) {
-        lane_frame L;
-        uint64_t base = (uint64_t)blockIdx.x * 256;
-        uint64_t nq = 0;
-        const uint8_t *nfb = pkts;
-        int32_t ncap = 0;
-        if (base < n) {
-            lane_desc(L, p, n, pkts, off, len, unit_log2);
-            nfb = L.fb;
-            ncap = L.cap;
-        }
-        for (; base < n; base += stride, p += stride) {
-            L.p = p;
-            L.valid = p < n;
-            L.fb = nfb;
-            L.cap = ncap;
-            lane_load<NTL>(L);
-            nq = p + stride; // descriptors of the next trip, in flight during this one
-            const uint64_t q = nq < n ? nq : 0;
-            nfb = pkts + ((uint64_t)off[q] << unit_log2);
-            ncap = nq < n ? (int32_t)len[q] : 0;
-            lane_process<0, ST_NT, NTL>(L, nullptr, ft, out, counts, hist, lds_bins);
-        }
-    } else {
-        lane_frame A, B;
-        uint64_t base = (uint64_t)blockIdx.x * 256;
-        if (base < n) {
-            lane_desc(A, p, n, pkts, off, len, unit_log2);
-            lane_load<NTL>(A);
-        }
-        // two frames alternate roles; the loop body is unrolled twice so that
-        // A and B stay in fixed registers
-        while (base < n) {
-            uint64_t nb = base + stride;
-            lane_desc(B, p + stride, n, pkts, off, len, unit_log2);
-            lane_process<0, ST_NT, NTL>(A, nb < n ? &B : nullptr, ft, out, counts, hist, lds_bins);
-            base = nb;
-            p += stride;
-            if (base >= n) break;
-            nb = base + stride;
-            lane_desc(A, p + stride, n, pkts, off, len, unit_log2);
-            lane_process<0, ST_NT, NTL>(B, nb < n ? &A : nullptr, ft, out, counts, hist, lds_bins);
-            base = nb;
-            p += stride;
-        }
     }
     if (lds_bins) {
         __syncthreads();
@@ -1338,7 +1255,7 @@ __global__ __launch_bounds__(256, PIPE == 2 ? 6 : 1) void rx_classify_lane_kerne
     }
 }
 
-template <int PIPE, int ABL = 0, bool ST_NT = true, bool NTL = true, bool LDT = false>
+template <int PIPE, int ABL = 0, bool NTL = true, bool LDT = false>
 hipError_t launch_lane(const uint8_t *pkts, const uint32_t *off, const uint16_t *len, uint32_t n,
                        uint32_t unit_log2, const rx_ft_dev &ft, uint4 *out,
                        unsigned long long *counts, uint32_t lds_bins, hipStream_t s,
@@ -1349,7 +1266,7 @@ hipError_t launch_lane(const uint8_t *pkts, const uint32_t *off, const uint16_t 
                        (PIPE == 12 || PIPE == 14 || PIPE >= 16 ? 16384u : 0u);
     int cu = 0, bpc = 0;
     hipError_t e = rx_occupancy(
-        reinterpret_cast<const void *>(rx_classify_lane_kernel<PIPE, ABL, ST_NT, NTL, LDT>), 256,
+        reinterpret_cast<const void *>(rx_classify_lane_kernel<PIPE, ABL, NTL, LDT>), 256,
         lds, &cu, &bpc);
     if (e != hipSuccess) return e;
     const uint64_t tiles = ((uint64_t)n + 255) / 256;
@@ -1358,23 +1275,24 @@ hipError_t launch_lane(const uint8_t *pkts, const uint32_t *off, const uint16_t 
     uint64_t blocks = (uint64_t)cu * occ;
     if (blocks > tiles) blocks = tiles;
     if (blocks == 0) blocks = 1;
-    hipLaunchKernelGGL((rx_classify_lane_kernel<PIPE, ABL, ST_NT, NTL, LDT>), dim3((uint32_t)blocks), dim3(256), lds, s,
+    hipLaunchKernelGGL((rx_classify_lane_kernel<PIPE, ABL, NTL, LDT>), dim3((uint32_t)blocks), dim3(256), lds, s,
                        pkts, off, len, n, unit_log2, ft, out, counts, lds_bins, idx, n_dev);
     return hipGetLastError();
 }
 
 
-// the LDS-table instantiation when the flow set has a compact UDP table
-template <int PIPE, int ABL = 0, bool ST_NT = true, bool NTL = true>
+// the LDS-table instantiation when the flow set has a compact UDP table (both
+// with plain per-lane frame loads, NTL = false)
+template <int PIPE, int ABL = 0>
 hipError_t launch_lane_udpc(const uint8_t *pkts, const uint32_t *off, const uint16_t *len,
                             uint32_t n, uint32_t unit_log2, const rx_ft_dev &ft, uint4 *out,
                             unsigned long long *counts, uint32_t lds_bins, hipStream_t s,
                             const uint32_t *idx = nullptr, const uint32_t *n_dev = nullptr) {
     if (ft.udpc)
-        return launch_lane<PIPE, ABL, ST_NT, NTL, true>(pkts, off, len, n, unit_log2, ft, out,
-                                                         counts, lds_bins, s, idx, n_dev);
-    return launch_lane<PIPE, ABL, ST_NT, NTL, false>(pkts, off, len, n, unit_log2, ft, out, counts,
-                                                      lds_bins, s, idx, n_dev);
+        return launch_lane<PIPE, ABL, false, true>(pkts, off, len, n, unit_log2, ft, out, counts,
+                                                   lds_bins, s, idx, n_dev);
+    return launch_lane<PIPE, ABL, false, false>(pkts, off, len, n, unit_log2, ft, out, counts,
+                                                lds_bins, s, idx, n_dev);
 }
 
 // ---------------------------------------------------------------------------
@@ -1462,7 +1380,7 @@ static hipError_t launch_binned(const uint8_t *pkts, const uint32_t *off, const 
     if ((e = hipGetLastError()) != hipSuccess) return e;
     rx_ft_dev fl = ft;
     if (!fl.bpc_cap) fl.bpc_cap = 6;
-    e = launch_lane_udpc<0, 0, true, false>(pkts, off, len, n, unit_log2, fl, out, counts, lds_bins, s,
+    e = launch_lane_udpc<0, 0>(pkts, off, len, n, unit_log2, fl, out, counts, lds_bins, s,
                                         lists, lens);
     if (e != hipSuccess) return e;
     return launch_v<8, 2, 1, 1>(pkts, off, len, n, unit_log2, ft, out, counts, lds_bins, s,
@@ -1488,18 +1406,9 @@ static hipError_t launch_binned(const uint8_t *pkts, const uint32_t *off, const 
 //   to per-thread tail loops: correct for any layout, fast for ordered ones
 //   (packed bursts, fixed slots).
 
-// inclusive prefix sum over the 64 lanes of a wave
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x) {
-    x += __builtin_amdgcn_update_dpp(0u, x, 0x111, 0xF, 0xF, true); // row_shr:1
-    x += __builtin_amdgcn_update_dpp(0u, x, 0x112, 0xF, 0xF, true); // row_shr:2
-    x += __builtin_amdgcn_update_dpp(0u, x, 0x114, 0xF, 0xF, true); // row_shr:4
-    x += __builtin_amdgcn_update_dpp(0u, x, 0x118, 0xF, 0xF, true); // row_shr:8
-    x += __builtin_amdgcn_update_dpp(0u, x, 0x142, 0xA, 0xF, false); // row_bcast:15 -> rows 1,3
-    x += __builtin_amdgcn_update_dpp(0u, x, 0x143, 0xC, 0xF, false); // row_bcast:31 -> rows 2,3
-    return x;
-}
-
-// N independent inclusive scans, step-interleaved: each DPP step of one
+// N independent inclusive prefix sums over the 64 lanes of a wave (row_shr:1,
+// 2, 4, 8, then row_bcast:15 into rows 1 and 3 and row_bcast:31 into rows 2
+// and 3), step-interleaved: each DPP step of one
 // row reads a register the previous VALU op did not write, so the DPP
 // read-after-write wait states (s_nop) of a single scan disappear
 template <int N>
@@ -1552,31 +1461,29 @@ __device__ __forceinline__ uint32_t chunk_sum(uint4 v) {
 // outstanding load (vmcnt(0)), which would serialise the tile prefetch.
 // ABL (diagnostic builds only, never selected automatically): 1 = no flow
 // table probe (flow id from the port: wrong verdicts by construction)
-// HO (issue order of the first tile against the flow probe): 0 = probe, then
-// the first tile's loads; 1 = the first tile's loads, then the probe (its
-// dependent slot reads overlap the tile in flight); 2 = the probe and the
-// verdict fields after the whole tail stream (the slot read's latency hides
-// behind the stream; the key words stay live across it); 3 = 2 at a register
-// budget for 5 resident blocks per CU instead of 6 (2 spills one VGPR at 6).
-// PW (first probe window): 1 = one slot; 2 = the home slot and the next one in
-// the same trip (the table keeps a mirror of slot 0 past its end), so a key
-// displaced by one slot costs no dependent second read.  B1: one barrier per
-// tail tile instead of two (a tile's boundary prefixes are read after the next
-// tile's barrier, which already orders them after their writes; s_pre and
-// s_wt are double-buffered, so the next writes to a buffer come a barrier
-// after its last reads)
-// FPB: frames per block (256, or 128 / 64 / 32 / 16 with the other threads
-// streaming only: shorter blocks for jumbo frames, whose 256-frame blocks
-// stream 2.3 MB each and leave the last round of blocks a fraction of the chip)
-// L: 16-B chunks per thread per tail tile (4: 16-KiB tiles)
-template <bool NTS, int ABL = 0, int HO = 0, int PW = 1, bool B1 = false, bool DS = false,
-          bool HG = false, uint32_t FPB = 256, int L = 4, bool WT = false>
+// HO (issue order of the flow probe against the tail stream): 0 = probe, then
+// the first tile's loads; 3 = the probe and the verdict fields after the whole
+// tail stream (the slot read's latency hides behind the stream; the key words
+// stay live across it), at a register budget for 5 resident blocks per CU
+// instead of 6 (at 6 it spills one VGPR).
+// B1: one barrier per tail tile instead of two (a tile's boundary prefixes are
+// read after the next tile's barrier, which already orders them after their
+// writes; s_pre and s_wt are double-buffered, so the next writes to a buffer
+// come a barrier after its last reads)
+// FPB: frames per block (256, or 32 / 16 with the other threads streaming
+// only: shorter blocks for jumbo frames, whose 256-frame blocks stream 2.3 MB
+// each and leave the last round of blocks a fraction of the chip)
+// The tail loads are non-temporal, 4 per thread per tile (16-KiB tiles); the
+// first probe window is one slot.
+template <int ABL = 0, int HO = 0, bool B1 = false, bool DS = false, bool HG = false,
+          uint32_t FPB = 256>
 __global__ __launch_bounds__(256, HO == 3 ? 5 : 6) void rx_classify_stream_kernel(
     const uint8_t *__restrict__ pkts, const uint32_t *__restrict__ off,
     const uint16_t *__restrict__ len, uint32_t n, uint32_t unit_log2, rx_ft_dev ft,
     uint4 *__restrict__ out, unsigned long long *__restrict__ counts, uint32_t lds_bins) {
     extern __shared__ __attribute__((aligned(16))) uint32_t hist[];
-    constexpr uint32_t LPT = L;          // 16-B chunks per thread per tail tile
+    static_assert(HO == 0 || HO == 3, "probe before or after the tail stream");
+    constexpr uint32_t LPT = 4;          // 16-B chunks per thread per tail tile
     constexpr uint32_t TCH = 256u * LPT; // chunks per tail tile
     __shared__ __attribute__((aligned(16))) uint32_t s_pre[2][TCH];
     __shared__ __attribute__((aligned(16))) uint32_t s_wt[2][4 * LPT]; // [row j][wave w]
@@ -1602,8 +1509,7 @@ __global__ __launch_bounds__(256, HO == 3 ? 5 : 6) void rx_classify_stream_kerne
     // frame: PMC r02g.)
     {
         const uint64_t tile = blockIdx.x;
-        static_assert(FPB == 256 || FPB == 128 || FPB == 64 || FPB == 32 || FPB == 16,
-                      "frames per block");
+        static_assert(FPB == 256 || FPB == 32 || FPB == 16, "frames per block");
         const uint64_t p = tile * FPB + tid;
         const bool valid = tid < FPB && p < n;
         const uint64_t q = valid ? p : 0;
@@ -1634,7 +1540,7 @@ __global__ __launch_bounds__(256, HO == 3 ? 5 : 6) void rx_classify_stream_kerne
 #pragma unroll
             for (int j = 0; j < LPT; ++j) {
                 const uint32_t k = c0 + j * 256 + tid;
-                v[j] = ldg16<NTS>(sb + ((uint64_t)(k < span ? k : 0) << 4)); // masked at use
+                v[j] = ldg16<true>(sb + ((uint64_t)(k < span ? k : 0) << 4)); // masked at use
             }
         };
         auto span_of = [&]() { // a span far larger than the tails means scattered frames
@@ -1716,7 +1622,9 @@ __global__ __launch_bounds__(256, HO == 3 ? 5 : 6) void rx_classify_stream_kerne
         const uint4 *sp0 = hash0 ? (is_udp ? ft.udp : ft.tcp) +
                                        (rx_hash3s(ft.hseed, ka, kb, kc) & (is_udp ? ft.udp_mask : ft.tcp_mask))
                                  : reinterpret_cast<const uint4 *>(fb);
-        static_assert(PW == 1 || PW == 2 || PW == 4, "probe window");
+        // slots of the first probe window (kept as one-trip loops over PW: the
+        // same probe written straight-line compiles to different code)
+        constexpr int PW = 1;
         uint4 sw[PW];
 #pragma unroll
         for (int w = 0; w < PW; ++w) sw[w] = ld_slot(sp0 + (hash0 ? w : 0));
@@ -1770,7 +1678,7 @@ __global__ __launch_bounds__(256, HO == 3 ? 5 : 6) void rx_classify_stream_kerne
             bool hashed = probe0;
             if (probe0 && udp_port) hashed = !rx_udp_port_decide(pe, ka, ft.udp_dip, &flow);
             if (hashed) {
-                // slot index and table recomputed from the keys (HO = 2 keeps only
+                // slot index and table recomputed from the keys (HO = 3 keeps only
                 // the keys and the first slot live across the stream)
                 const uint4 *tb = is_udp ? ft.udp : ft.tcp;
                 const uint32_t mk = is_udp ? ft.udp_mask : ft.tcp_mask;
@@ -1796,7 +1704,7 @@ __global__ __launch_bounds__(256, HO == 3 ? 5 : 6) void rx_classify_stream_kerne
                         }
                     }
                 }
-                while (!done) { // past the window, or a UDP key on a shared port
+                while (!done) { // past that slot, or a UDP key on a shared port
                     const uint4 sl = ld_slot(tb + pj);
                     if (sl.w == RX_SLOT_EMPTY) break;
                     if (sl.x == ka && sl.y == kb && sl.z == kc) {
@@ -1817,7 +1725,6 @@ __global__ __launch_bounds__(256, HO == 3 ? 5 : 6) void rx_classify_stream_kerne
         if constexpr (HO == 0) probe_flow();
         // ---- tail phase -------------------------------------------------------
         if constexpr (!DS) tile_load(va, 0);
-        if constexpr (HO == 1) probe_flow();
         if (streamed) {
             const uint32_t cs = tail ? (uint32_t)(cs_abs - lo) : 0xFFFFFFFFu;
             const uint32_t ce = tail ? (uint32_t)(ce_abs - lo) : 0xFFFFFFFFu;
@@ -1896,7 +1803,7 @@ __global__ __launch_bounds__(256, HO == 3 ? 5 : 6) void rx_classify_stream_kerne
             }
         }
 
-        if constexpr (HO >= 2) probe_flow();
+        if constexpr (HO == 3) probe_flow();
         // ---- verdict ----------------------------------------------------------
         uint32_t ck = 0;
         if (do_sum) {
@@ -1917,7 +1824,7 @@ __global__ __launch_bounds__(256, HO == 3 ? 5 : 6) void rx_classify_stream_kerne
             vd.y = vy;
             vd.z = ck | (cl << 16) | (((uint32_t)rc & 0xFFu) << 24);
             vd.w = (ok ? 1u : 0u) | (flags << 8) | (stored << 16);
-            st_verdict<WT>(ft, out, p, vd);
+            st_verdict(ft, out, p, vd);
             lane_count(cidx, counts, hist, lds_bins);
         }
         // (FPB < 64: the first FPB lanes of wave 0; its other lanes' pieces are the next block's)
@@ -1932,15 +1839,15 @@ __global__ __launch_bounds__(256, HO == 3 ? 5 : 6) void rx_classify_stream_kerne
     }
 }
 
-template <bool NTS, int ABL = 0, int HO = 0, int PW = 1, bool B1 = false, bool DS = false,
-          bool HG = false, uint32_t FPB = 256, int L = 4, bool WT = false>
+template <int ABL = 0, int HO = 0, bool B1 = false, bool DS = false, bool HG = false,
+          uint32_t FPB = 256>
 hipError_t launch_stream(const uint8_t *pkts, const uint32_t *off, const uint16_t *len, uint32_t n,
                          uint32_t unit_log2, const rx_ft_dev &ft, uint4 *out,
                          unsigned long long *counts, uint32_t lds_bins, hipStream_t s,
                          const uint32_t *, const uint32_t *) {
     const uint64_t blocks = ((uint64_t)n + FPB - 1) / FPB;
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((rx_classify_stream_kernel<NTS, ABL, HO, PW, B1, DS, HG, FPB, L, WT>), dim3((uint32_t)blocks),
+    hipLaunchKernelGGL((rx_classify_stream_kernel<ABL, HO, B1, DS, HG, FPB>), dim3((uint32_t)blocks),
                        dim3(256), (size_t)lds_bins * 4u, s, pkts, off, len, n, unit_log2, ft, out,
                        counts, lds_bins);
     return hipGetLastError();
@@ -1978,7 +1885,10 @@ hipError_t launch_stream(const uint8_t *pkts, const uint32_t *off, const uint16_
 //  - a span of scattered frames or one larger than the map (SH_MAPC chunks):
 //    per-thread head loads and tail loops.
 // LDS 31.9 KiB per block (map 7.25, heads 16, prefixes 8): 5 blocks per CU.
-constexpr uint32_t SH_MAPC = 7424; // span chunks the head map covers (116 KiB)
+// span chunks the head map covers (116 KiB).  (A map for 256 frames of 1500 B,
+// 388 KiB of span at 3 blocks/CU, ran cfg3 at 1.161 vs 1.042 ms for the G=8
+// group kernel: profiles/r02ac.)
+constexpr uint32_t SH_MAPC = 7424;
 
 // header fields of a frame head (the first 64 B, bytes past caplen zeroed)
 struct sh_head {
@@ -2086,10 +1996,8 @@ __device__ __forceinline__ uint32_t sh_head_sum(const uint4 (&c)[4], const sh_he
 // store.  PW: slots of the first probe window
 // (1, 2 or 4 consecutive slots of the hashed table loaded together; the table
 // mirrors its first slots past its end), so a displaced key costs no dependent
-// second round trip at the end of the block (pipes 60 / 63 / 64).
-// MAPC: span chunks the head map covers.  (A map for 256 frames of 1500 B,
-// 388 KiB of span at 3 blocks/CU, ran cfg3 at 1.161 vs 1.042 ms for the G=8
-// group kernel: profiles/r02ac.)
+// second round trip at the end of the block (pipes 60 / 75 / 64).
+// L: 16-B chunks per thread per stream tile (4 / 3 / 2: 16- / 12- / 8-KiB tiles).
 // EP (pipe 65): every frame's probe is issued as soon as its head is known,
 // inside the stream, instead of after it, so the block no longer ends on the
 // probe round trip.  A frame whose head completes in tile t < last has it
@@ -2097,8 +2005,8 @@ __device__ __forceinline__ uint32_t sh_head_sum(const uint4 (&c)[4], const sh_he
 // block's LAST tile ("early") has its four head chunks loaded at the block
 // start by LDS-DMA (no VGPRs held through the stream; its head chunks are not
 // marked in the map) and parsed after tile 0.  The parsed head is kept as 7
-// words per lane; the probe window (PW <= 3 slots) is loaded by LDS-DMA into
-// the frame's own head slots 1..3, which the parse has freed (s_hd is
+// words per lane; the probe window (PW <= 2 slots) is loaded by LDS-DMA into
+// the frame's own head slots 1..2, which the parse has freed (s_hd is
 // slot-major, [k][256], so one wave's slot k is the lane-linear 1 KiB an
 // LDS-DMA instruction writes).  An early frame's s_rel carries bit 15, so the
 // stream never takes one of its chunks for a head chunk (a chunk no frame
@@ -2107,17 +2015,8 @@ __device__ __forceinline__ uint32_t sh_head_sum(const uint4 (&c)[4], const sh_he
 // the capture, from s_cp) into s_psum instead of storing the chunk in head
 // slot 0, so a head takes 48 B of LDS instead of 64 (with 8-KiB tiles the
 // block fits 6 per CU: 26.1 KiB).
-// FPB: frames per block (a multiple of 64; threads past it only stream), so
-// that larger frames still fit the head map (1500 B: 64 frames, 96 KiB).
-// TT: stream tiles in flight per thread (2, or 3 with a period-3 rotation).
-// PERS: a resident grid; each block loops over block-tiles of FPB frames and
-// loads the next one's descriptors during the current one's stream, so no
-// block starts on a descriptor round trip (and the LDS histogram is flushed
-// once per block instead of once per 256 frames).
-// WT: write-through (sc1) verdict stores (the G=8 kernel's pipe 40).
-template <int ABL = 0, int PW = 1, uint32_t MAPC = SH_MAPC, bool EP = false, int L = EP ? 3 : 4,
-          bool PS = false, int FPB = 256, int TT = 2, bool PERS = false, bool WT = false>
-__global__ __launch_bounds__(256, MAPC > SH_MAPC ? 3 : (PS && L == 2 ? 6 : 5)) void rx_classify_sh_kernel(
+template <int ABL = 0, int PW = 1, bool EP = false, int L = EP ? 3 : 4, bool PS = false>
+__global__ __launch_bounds__(256, PS && L == 2 ? 6 : 5) void rx_classify_sh_kernel(
     const uint8_t *__restrict__ pkts, const uint32_t *__restrict__ off,
     const uint16_t *__restrict__ len, uint32_t n, uint32_t unit_log2, rx_ft_dev ft,
     uint4 *__restrict__ out, unsigned long long *__restrict__ counts, uint32_t lds_bins) {
@@ -2128,7 +2027,7 @@ __global__ __launch_bounds__(256, MAPC > SH_MAPC ? 3 : (PS && L == 2 ? 6 : 5)) v
     constexpr uint32_t TCH = 256u * LPT; // chunks per tile (16 KiB)
     __shared__ __attribute__((aligned(16))) uint32_t s_pre[2][TCH];
     __shared__ __attribute__((aligned(16))) uint32_t s_wt[2][4 * LPT]; // [row j][wave w]
-    __shared__ __attribute__((aligned(16))) uint8_t s_map[MAPC];
+    __shared__ __attribute__((aligned(16))) uint8_t s_map[SH_MAPC];
     static_assert(!(EP && PS), "EP keeps chunk 0 in head slot 0");
     __shared__ __attribute__((aligned(16))) uint4 s_hd[256 * (PS ? 3 : 4)];
     __shared__ uint32_t s_psum[PS ? 256 : 1]; // PS: each frame's partial-chunk sum
@@ -2144,21 +2043,12 @@ __global__ __launch_bounds__(256, MAPC > SH_MAPC ? 3 : (PS && L == 2 ? 6 : 5)) v
         return EP ? k * 256u + m : (PS ? (k - 1u) * 256u + m : m * 4u + k);
     };
     for (uint32_t i = tid; i < lds_bins; i += 256) hist[i] = 0;
-    static_assert(FPB % 64 == 0 && FPB <= 256, "whole waves of frames");
-    const uint32_t nblk = (uint32_t)(((uint64_t)n + FPB - 1) / FPB);
-    // PERS: this block-tile's descriptors, loaded during the previous one
-    uint32_t nx_off = 0;
-    int32_t nx_len = 0;
-    auto desc_load = [&](uint32_t blk) {
-        const uint64_t pp = (uint64_t)blk * FPB + tid;
-        const bool vv = blk < nblk && tid < (uint32_t)FPB && pp < n;
-        nx_off = off[vv ? pp : 0];
-        nx_len = vv ? (int32_t)len[vv ? pp : 0] : 0;
-    };
-    if constexpr (PERS) desc_load(blockIdx.x);
-    // (without PERS the loop is one trip the compiler sees as such)
-    const uint32_t bend = PERS ? nblk : blockIdx.x + 1u;
-    for (uint32_t blk = blockIdx.x; blk < bend; blk += PERS ? gridDim.x : 1u) {
+    // one tile of FPB frames per block, written as a loop of one trip (the
+    // compiler sees it as such; straight-line code compiles differently, and
+    // so does dropping the tests against FPB that the thread count implies)
+    constexpr int FPB = 256;
+    const uint32_t bend = blockIdx.x + 1u;
+    for (uint32_t blk = blockIdx.x; blk < bend; blk += 1u) {
     if (tid == 0) {
         s_lo = ~0ull;
         s_hi = 0;
@@ -2168,23 +2058,14 @@ __global__ __launch_bounds__(256, MAPC > SH_MAPC ? 3 : (PS && L == 2 ? 6 : 5)) v
     if (tid < 16) s_et[tid] = 0;
     {
         uint4 *m4 = reinterpret_cast<uint4 *>(s_map);
-        for (uint32_t i = tid; i < MAPC / 16; i += 256) m4[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
+        for (uint32_t i = tid; i < SH_MAPC / 16; i += 256) m4[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
     }
     const uint64_t p = (uint64_t)blk * FPB + tid;
     const bool valid = tid < (uint32_t)FPB && p < n;
     const uint64_t q = valid ? p : 0;
-    uint32_t doff;
-    int32_t dlen;
-    if constexpr (PERS) {
-        doff = nx_off;
-        dlen = nx_len;
-        desc_load(blk + gridDim.x); // in flight through this block-tile's stream
-    } else {
-        doff = off[q];
-        dlen = valid ? (int32_t)len[q] : 0;
-    }
+    const uint32_t doff = off[q];
+    const int32_t cp = valid ? (int32_t)len[q] : 0;
     const uint64_t fpos = (uint64_t)doff << unit_log2;
-    const int32_t cp = dlen;
     const uint8_t *fb = pkts + fpos;
     const uint64_t fc = fpos >> 4;                  // first chunk (absolute)
     const uint32_t nch = ((uint32_t)cp + 15u) >> 4; // chunks of the capture
@@ -2195,7 +2076,7 @@ __global__ __launch_bounds__(256, MAPC > SH_MAPC ? 3 : (PS && L == 2 ? 6 : 5)) v
     __syncthreads();
     const uint64_t lo = s_lo, hi = s_hi;
     const uint32_t tsum = s_tail;
-    const bool streamed = hi > lo && hi - lo <= MAPC && hi - lo <= 2ull * tsum + TCH;
+    const bool streamed = hi > lo && hi - lo <= SH_MAPC && hi - lo <= 2ull * tsum + TCH;
     const uint32_t span = streamed ? (uint32_t)(hi - lo) : 0u;
     const uint8_t *sb = streamed ? pkts + (lo << 4) : fb;
     auto tile_load = [&](uint4 *v, uint32_t c0) {
@@ -2215,7 +2096,7 @@ __global__ __launch_bounds__(256, MAPC > SH_MAPC ? 3 : (PS && L == 2 ? 6 : 5)) v
     // (tlast >= 2: the early parse runs after the first tile pair, which must
     // not hold the last tile, whose partial chunks land in head slot 0)
     const bool early = EP && streamed && cp >= 14 && tlast >= 2 && thead == tlast;
-    const uint32_t relx = early ? 0x8000u : 0u; // (rel < MAPC < 0x8000)
+    const uint32_t relx = early ? 0x8000u : 0u; // (rel < SH_MAPC < 0x8000)
     if (streamed) {
         if (!early)
             for (uint32_t k = 0; k < nh; ++k) s_map[rel + k] = (uint8_t)tid;
@@ -2380,28 +2261,13 @@ __global__ __launch_bounds__(256, MAPC > SH_MAPC ? 3 : (PS && L == 2 ? 6 : 5)) v
             }
         }
     };
-    static_assert(TT == 2 || (TT == 3 && !EP), "tiles in flight");
     uint32_t c0 = 0;
-    if constexpr (TT == 3) { // tile t in buffer t & 1, three tiles of loads in flight
-        uint4 vc[LPT];
-        tile_load(vb, TCH);
-        for (; c0 < span; c0 += 3 * TCH) {
-            const uint32_t t0 = c0 / TCH;
-            tile_load(vc, c0 + 2 * TCH);
-            stile(va, c0, t0 & 1u);
-            tile_load(va, c0 + 3 * TCH);
-            stile(vb, c0 + TCH, (t0 + 1u) & 1u);
-            tile_load(vb, c0 + 4 * TCH);
-            stile(vc, c0 + 2 * TCH, t0 & 1u);
-        }
-    } else {
-        for (; c0 < span; c0 += 2 * TCH) {
-            tile_load(vb, c0 + TCH);
-            stile(va, c0, 0);
-            tile_load(va, c0 + 2 * TCH);
-            stile(vb, c0 + TCH, 1);
-            ep_issue(c0); // the heads completed in this pair of tiles
-        }
+    for (; c0 < span; c0 += 2 * TCH) {
+        tile_load(vb, c0 + TCH);
+        stile(va, c0, 0);
+        tile_load(va, c0 + 2 * TCH);
+        stile(vb, c0 + TCH, 1);
+        ep_issue(c0); // the heads completed in this pair of tiles
     }
     __syncthreads(); // the last tile's prefixes and every head slot written
     if constexpr (EP) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the windows landed
@@ -2550,13 +2416,12 @@ __global__ __launch_bounds__(256, MAPC > SH_MAPC ? 3 : (PS && L == 2 ? 6 : 5)) v
         if constexpr ((ABL & 64) != 0) // diagnostic: no verdict store
             asm volatile("" ::"v"(vd.x), "v"(vd.y), "v"(vd.z), "v"(vd.w));
         else
-            st_verdict<WT>(ft, out, p, vd);
+            st_verdict(ft, out, p, vd);
         lane_count(cidx, counts, hist, lds_bins);
     }
     if constexpr ((ABL & 48) == 0)
         if (wvu * 64u < (uint32_t)FPB) put_count_idx_wave(ft, p, cidx, lane); // (waves of frames)
-    if constexpr (PERS) __syncthreads(); // every LDS read of this block-tile done
-    } // block-tiles
+    } // the block's tile
     if (lds_bins) {
         __syncthreads();
         for (uint32_t i = tid; i < lds_bins; i += 256) {
@@ -2566,27 +2431,17 @@ __global__ __launch_bounds__(256, MAPC > SH_MAPC ? 3 : (PS && L == 2 ? 6 : 5)) v
     }
 }
 
-template <int ABL = 0, int PW = 1, uint32_t MAPC = SH_MAPC, bool EP = false, int L = EP ? 3 : 4,
-          bool PS = false, int FPB = 256, int TT = 2, bool PERS = false, bool WT = false>
+template <int ABL = 0, int PW = 1, bool EP = false, int L = EP ? 3 : 4, bool PS = false>
 hipError_t launch_sh(const uint8_t *pkts, const uint32_t *off, const uint16_t *len, uint32_t n,
                      uint32_t unit_log2, const rx_ft_dev &ft, uint4 *out,
                      unsigned long long *counts, uint32_t lds_bins, hipStream_t s,
                      const uint32_t *, const uint32_t *) {
-    uint64_t blocks = ((uint64_t)n + FPB - 1) / FPB;
+    const uint64_t blocks = ((uint64_t)n + 255) / 256;
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    if (PERS) { // one resident wave of blocks
-        int cu = 0, bpc = 0;
-        hipError_t e = rx_occupancy(
-            reinterpret_cast<const void *>(rx_classify_sh_kernel<ABL, PW, MAPC, EP, L, PS, FPB, TT, PERS, WT>),
-            256, (size_t)lds_bins * 4u, &cu, &bpc);
-        if (e != hipSuccess) return e;
-        const uint64_t res = (uint64_t)cu * (uint64_t)(bpc > 0 ? bpc : 1);
-        if (blocks > res) blocks = res;
-    }
     if (EP && ((uintptr_t)pkts & 15u)) // LDS-DMA needs 16-B aligned frames: pipe 64 instead
-        return launch_sh<ABL, 4, MAPC, false>(pkts, off, len, n, unit_log2, ft, out, counts,
-                                              lds_bins, s, nullptr, nullptr);
-    hipLaunchKernelGGL((rx_classify_sh_kernel<ABL, PW, MAPC, EP, L, PS, FPB, TT, PERS, WT>), dim3((uint32_t)blocks),
+        return launch_sh<ABL, 4, false>(pkts, off, len, n, unit_log2, ft, out, counts, lds_bins, s,
+                                        nullptr, nullptr);
+    hipLaunchKernelGGL((rx_classify_sh_kernel<ABL, PW, EP, L, PS>), dim3((uint32_t)blocks),
                        dim3(256),
                        (size_t)lds_bins * 4u, s, pkts, off, len, n, unit_log2, ft, out, counts,
                        lds_bins);
@@ -3150,13 +3005,14 @@ struct variant_entry {
     uint32_t bpc; // default resident blocks per CU (0 = occupancy), from measurement
 };
 // every compiled variant; the first entry per lanes-per-frame g is its default.
-// g = 1 (one frame per lane): p = 4 chunks up front, pipe = prefetch mode
-// (0 none, 1 descriptors + frame one trip ahead, 2 = 1 capped at 6 waves/SIMD,
-// 3 descriptors only, 4 = 0 with plain verdict stores, 5/6 = 0/4 with plain
-// frame loads, 7/8 = 1/2 with plain frame loads, 9/10 = ordered one-trip
-// descriptor prefetch + deferred store, nt / plain store); g >= 4: pipe 0/1 = no /
-// one-trip pipeline, 2/3 = 0/1 with plain frame loads; pipe >= 100 are
-// diagnostic ablations (wrong verdicts by construction, tuning only).
+// g = 1 (one frame per lane): p = 4 chunks up front, pipe = the lane kernel's
+// PIPE (0: load, process, repeat; 12: heads staged through LDS; 14 and up: 12
+// software-pipelined, as the entries say), 5 = 0 with plain frame loads and
+// the LDS UDP table, 13 = 12 without that table; g >= 4: pipe 0/1 = no /
+// one-trip pipeline, 40 and up = 0 with write-through and write-batched
+// verdict stores; g = 0: the stream (30-54, 738, 938), SH (60-75) and WC
+// (80-83) kernels; pipe >= 100 are diagnostic ablations (wrong verdicts by
+// construction, tuning only).
 static const variant_entry k_variants[] = {
     // The product table: the four defaults (rx_pick_variant) and the measured
     // alternatives next to them, every one parity-tested (tests/
@@ -3170,39 +3026,39 @@ static const variant_entry k_variants[] = {
     // pipe 12 at 4 blocks/CU: with per-flow counts its LDS (stage + UDP table +
     // histogram) allows 4 anyway; without counts 5 fit and ran 36% slower
     // (r01g: 0.255 vs 0.346 ms on cfg2, profiles/r01g/sweep_lane_bpc_counts.txt)
-    {1, 4, 1, 12, launch_lane_udpc<12, 0, true, false>, 4},
+    {1, 4, 1, 12, launch_lane_udpc<12, 0>, 4},
     // 5: per-lane head loads, LDS UDP table (the binned path's small-frame kernel)
-    {1, 4, 1, 5, launch_lane_udpc<0, 0, true, false>, 6},
+    {1, 4, 1, 5, launch_lane_udpc<0, 0>, 6},
     // 14 (the 64-B default): 12 software-pipelined (descriptors two trips,
     // frame bytes one trip ahead)
-    {1, 4, 1, 14, launch_lane_udpc<14, 0, true, false>, 2},
+    {1, 4, 1, 14, launch_lane_udpc<14, 0>, 2},
     // 19: two adjacent 256-frame tiles per trip, both tiles' frame bytes
     // issued at the top of the trip, descriptors one trip ahead (the
     // byte-pattern ceiling's shape); 25 (the 64-B default from round 6): the
     // same with the trip's two tiles a grid stride apart, 0.2242-0.2248 vs
     // 0.2263-0.2268 ms per step for 19 (profiles/r06az)
-    {1, 4, 1, 19, launch_lane_udpc<19, 0, true, false>, 2},
-    {1, 4, 1, 25, launch_lane_udpc<25, 0, true, false>, 2},
+    {1, 4, 1, 19, launch_lane_udpc<19, 0>, 2},
+    {1, 4, 1, 25, launch_lane_udpc<25, 0>, 2},
     // 16 (the 64-B default for 8-B verdicts): 14 with lane_verdict_fast, 18%
     // fewer vector and half the scalar instructions; with 16-B verdicts the
     // same time as 14 (the stores bound it: profiles/r06ab, r06ac), with
     // 8-B verdicts 79.0-79.5 vs 76.2-77.4 Gpps for 14 (profiles/r06ak)
-    {1, 4, 1, 16, launch_lane_udpc<16, 0, true, false>, 2},
+    {1, 4, 1, 16, launch_lane_udpc<16, 0>, 2},
     {1, 4, 1, 0, launch_lane<0>},
     // group kernels, one per G (the first entry per g is its default)
     {4, 1, 1, 1, launch_v<4, 1, 1, 1>},
     {8, 2, 2, 0, launch_v<8, 2, 2, 0>},
     // 40 (the 1500-B default): G=8 with write-through verdict stores (sc1:
     // the lines leave the L2 instead of staying in it)
-    {8, 2, 2, 40, launch_v<8, 2, 2, 0, true, 0, 1, true>},
+    {8, 2, 2, 40, launch_v<8, 2, 2, 0, 0, 1, true>},
     // 41 / 42: 40 write-batched (WB): each block owns contiguous tiles and
     // writes the verdicts of 16 / 32 of them (16 / 32 KiB) at once (sc1)
-    {8, 2, 2, 41, launch_v<8, 2, 2, 0, true, 0, 1, true, 16>},
-    {8, 2, 2, 42, launch_v<8, 2, 2, 0, true, 0, 1, true, 32>},
+    {8, 2, 2, 41, launch_v<8, 2, 2, 0, 0, 1, true, 16>},
+    {8, 2, 2, 42, launch_v<8, 2, 2, 0, 0, 1, true, 32>},
     // 48 (the 1500-B default): 24 tiles per batch with the per-block histogram
     // in 16-bit bin pairs (32 KiB of LDS at 4097 flows, as 41's), the 32-bit
     // histogram when a block's share reaches 65536 frames
-    {8, 2, 2, 48, launch_v<8, 2, 2, 0, true, 0, 1, true, 24, true>},
+    {8, 2, 2, 48, launch_v<8, 2, 2, 0, 0, 1, true, 24, true>},
     {8, 2, 1, 0, launch_v<8, 2, 1, 0>},
     {16, 2, 2, 0, launch_v<16, 2, 2, 0>},
     {32, 3, 2, 0, launch_v<32, 3, 2, 0>},
@@ -3210,90 +3066,90 @@ static const variant_entry k_variants[] = {
     // g = 0: stream kernel (head per lane, tails streamed per block); 30: nt
     // tail loads; 38: probe after the stream, one barrier per tail tile (B1);
     // 738 / 938 (the jumbo default): 38 with 32 / 16 frames per block
-    {0, 1, 1, 30, launch_stream<true>},
-    {0, 1, 1, 38, launch_stream<true, 0, 3, 1, true>},
-    {0, 1, 1, 738, launch_stream<true, 0, 3, 1, true, false, false, 32>},
-    {0, 1, 1, 938, launch_stream<true, 0, 3, 1, true, false, false, 16>},
+    {0, 1, 1, 30, launch_stream<>},
+    {0, 1, 1, 38, launch_stream<0, 3, true>},
+    {0, 1, 1, 738, launch_stream<0, 3, true, false, false, 32>},
+    {0, 1, 1, 938, launch_stream<0, 3, true, false, false, 16>},
     // SH kernel (heads taken out of the block stream): 60; 64: a four-slot
     // first probe window; 67 (the IMIX default): 64 with 8-KiB tiles
     {0, 1, 1, 60, launch_sh<0>},
     {0, 1, 1, 64, launch_sh<0, 4>},
-    {0, 1, 1, 67, launch_sh<0, 4, SH_MAPC, false, 2>},
+    {0, 1, 1, 67, launch_sh<0, 4, false, 2>},
 #if RX_DIAG
     // ---- tuning shapes (correct verdicts; sweeps in profiles/) ----
-    {1, 4, 1, 13, launch_lane<12, 0, true, false>, 6}, // 12 without the LDS UDP table
+    {1, 4, 1, 13, launch_lane<12, 0, false>, 6}, // 12 without the LDS UDP table
     // two adjacent tiles per trip (19, the 64-B default) with
     // lane_verdict_fast: 0.2326 vs 0.2240 ms for 19 (profiles/r06ad)
-    {1, 4, 1, 18, launch_lane_udpc<18, 0, true, false>, 2},
-    {1, 4, 1, 23, launch_lane_udpc<23, 0, true, false>, 2}, // 19, both tiles' stores at the trip's end
-    {1, 4, 1, 24, launch_lane_udpc<24, 0, true, false>, 2}, // 19, next descriptors before the frames
-    {1, 4, 1, 21, launch_lane_udpc<21, 0, true, false>, 2}, // three tiles per trip
-    {1, 4, 1, 22, launch_lane_udpc<22, 0, true, false>, 2}, // four
+    {1, 4, 1, 18, launch_lane_udpc<18, 0>, 2},
+    {1, 4, 1, 23, launch_lane_udpc<23, 0>, 2}, // 19, both tiles' stores at the trip's end
+    {1, 4, 1, 24, launch_lane_udpc<24, 0>, 2}, // 19, next descriptors before the frames
+    {1, 4, 1, 21, launch_lane_udpc<21, 0>, 2}, // three tiles per trip
+    {1, 4, 1, 22, launch_lane_udpc<22, 0>, 2}, // four
     {8, 2, 2, 1, launch_v<8, 2, 2, 1>},
     {16, 2, 1, 0, launch_v<16, 2, 1, 0>},
     // write-batched G=8 around pipe 41 (WB 16, sc1): WB 8 / 12 / 24 (sc1), 16 (nt)
-    {8, 2, 2, 43, launch_v<8, 2, 2, 0, true, 0, 1, true, 8>},
-    {8, 2, 2, 44, launch_v<8, 2, 2, 0, true, 0, 1, true, 12>},
-    {8, 2, 2, 45, launch_v<8, 2, 2, 0, true, 0, 1, false, 16>},
-    {8, 2, 2, 46, launch_v<8, 2, 2, 0, true, 0, 1, true, 24>},
+    {8, 2, 2, 43, launch_v<8, 2, 2, 0, 0, 1, true, 8>},
+    {8, 2, 2, 44, launch_v<8, 2, 2, 0, 0, 1, true, 12>},
+    {8, 2, 2, 45, launch_v<8, 2, 2, 0, 0, 1, false, 16>},
+    {8, 2, 2, 46, launch_v<8, 2, 2, 0, 0, 1, true, 24>},
     // ... with a 16-bit histogram (half its LDS): WB 16 / 32 (24: pipe 48, the default)
-    {8, 2, 2, 47, launch_v<8, 2, 2, 0, true, 0, 1, true, 16, true>},
-    {8, 2, 2, 49, launch_v<8, 2, 2, 0, true, 0, 1, true, 32, true>},
+    {8, 2, 2, 47, launch_v<8, 2, 2, 0, 0, 1, true, 16, true>},
+    {8, 2, 2, 49, launch_v<8, 2, 2, 0, 0, 1, true, 32, true>},
     // ... five blocks per CU: pipe 48 needs 103 VGPRs and 32,784 B of LDS at
     // 4097 flows (both just above a fifth of the CU), so it runs 4 per CU.
     // WB 23 / 20 with the register budget of 5 blocks (MINW 5: <= 96 VGPRs)
     // fit 5; WB 23 at 4 blocks isolates the batch depth
-    {8, 2, 2, 50, launch_v<8, 2, 2, 0, true, 0, 5, true, 23, true>},
-    {8, 2, 2, 51, launch_v<8, 2, 2, 0, true, 0, 5, true, 20, true>},
-    {8, 2, 2, 52, launch_v<8, 2, 2, 0, true, 0, 1, true, 23, true>},
-    {8, 2, 2, 53, launch_v<8, 2, 2, 0, true, 0, 5, true, 16, true>},
+    {8, 2, 2, 50, launch_v<8, 2, 2, 0, 0, 5, true, 23, true>},
+    {8, 2, 2, 51, launch_v<8, 2, 2, 0, 0, 5, true, 20, true>},
+    {8, 2, 2, 52, launch_v<8, 2, 2, 0, 0, 1, true, 23, true>},
+    {8, 2, 2, 53, launch_v<8, 2, 2, 0, 0, 5, true, 16, true>},
     // pipe 48 with the remaining passes of both frames loaded together, 2 / 4
     // / 10 per frame per batch (RI)
-    {8, 2, 2, 54, launch_v<8, 2, 2, 0, true, 2, 1, true, 24, true>},
-    {8, 2, 2, 55, launch_v<8, 2, 2, 0, true, 4, 1, true, 24, true>},
-    {8, 2, 2, 56, launch_v<8, 2, 2, 0, true, 10, 1, true, 24, true>},
-    {0, 1, 1, 54, launch_stream<true, 0, 3, 1, true, false, true>}, // heads gathered 4 lanes/head
-    {0, 1, 1, 66, launch_sh<0, 4, SH_MAPC, false, 3>},              // 12-KiB tiles
-    {0, 1, 1, 68, launch_sh<0, 4, SH_MAPC, false, 2, true>},        // partial sums in the stream
-    {0, 1, 1, 75, launch_sh<0, 2, SH_MAPC, false, 2>},              // two-slot window
-    {0, 1, 1, 65, launch_sh<0, 2, SH_MAPC, true>},                  // probes inside the stream
+    {8, 2, 2, 54, launch_v<8, 2, 2, 0, 2, 1, true, 24, true>},
+    {8, 2, 2, 55, launch_v<8, 2, 2, 0, 4, 1, true, 24, true>},
+    {8, 2, 2, 56, launch_v<8, 2, 2, 0, 10, 1, true, 24, true>},
+    {0, 1, 1, 54, launch_stream<0, 3, true, false, true>}, // heads gathered 4 lanes/head
+    {0, 1, 1, 66, launch_sh<0, 4, false, 3>},              // 12-KiB tiles
+    {0, 1, 1, 68, launch_sh<0, 4, false, 2, true>},        // partial sums in the stream
+    {0, 1, 1, 75, launch_sh<0, 2, false, 2>},              // two-slot window
+    {0, 1, 1, 65, launch_sh<0, 2, true>},                  // probes inside the stream
     // ---- ablations: wrong verdicts (or counts) by construction ----
     // lane kernel (ABL bits: 1 = no bucket probe, 4 = no verdict store, 8 = no
     // checksum arithmetic): 101, 104, 108, 113 = 1|4|8; 2xx: the same with
     // plain frame loads at 6 blocks/CU
     {1, 4, 1, 101, launch_lane<0, 1>},     {1, 4, 1, 104, launch_lane<0, 4>},
     {1, 4, 1, 108, launch_lane<0, 8>},     {1, 4, 1, 113, launch_lane<0, 13>},
-    {1, 4, 1, 201, launch_lane<0, 1, true, false>, 6}, {1, 4, 1, 204, launch_lane<0, 4, true, false>, 6},
-    {1, 4, 1, 213, launch_lane<0, 13, true, false>, 6},
+    {1, 4, 1, 201, launch_lane<0, 1, false>, 6}, {1, 4, 1, 204, launch_lane<0, 4, false>, 6},
+    {1, 4, 1, 213, launch_lane<0, 13, false>, 6},
     // the 64-B default (pipe 14) with the same ablations (round 6): 1401 no
     // probe, 1404 no verdict store, 1408 no checksum arithmetic, 1413 = all three
-    {1, 4, 1, 1401, launch_lane_udpc<14, 1, true, false>, 2},
-    {1, 4, 1, 1404, launch_lane_udpc<14, 4, true, false>, 2},
-    {1, 4, 1, 1408, launch_lane_udpc<14, 8, true, false>, 2},
-    {1, 4, 1, 1413, launch_lane_udpc<14, 13, true, false>, 2},
-    {1, 4, 1, 1604, launch_lane_udpc<16, 4, true, false>, 2}, // pipe 16, no verdict store
+    {1, 4, 1, 1401, launch_lane_udpc<14, 1>, 2},
+    {1, 4, 1, 1404, launch_lane_udpc<14, 4>, 2},
+    {1, 4, 1, 1408, launch_lane_udpc<14, 8>, 2},
+    {1, 4, 1, 1413, launch_lane_udpc<14, 13>, 2},
+    {1, 4, 1, 1604, launch_lane_udpc<16, 4>, 2}, // pipe 16, no verdict store
     // stream kernel: no flow probe (130); pipe 46 (span from the descriptors)
     // and its ablations: no probe (146), no tail stream (246), no head loads
     // (446), neither heads nor stream (646); pipe 38: no head loads (438), no
     // partial-chunk load (838), neither (1238)
-    {0, 1, 1, 130, launch_stream<true, 1>},
-    {0, 1, 1, 46, launch_stream<true, 0, 3, 1, true, true>},
-    {0, 1, 1, 146, launch_stream<true, 1, 3, 1, true, true>},
-    {0, 1, 1, 246, launch_stream<true, 2, 3, 1, true, true>},
-    {0, 1, 1, 446, launch_stream<true, 4, 3, 1, true, true>},
-    {0, 1, 1, 646, launch_stream<true, 6, 3, 1, true, true>},
-    {0, 1, 1, 438, launch_stream<true, 4, 3, 1, true>}, {0, 1, 1, 838, launch_stream<true, 8, 3, 1, true>},
-    {0, 1, 1, 1238, launch_stream<true, 12, 3, 1, true>},
+    {0, 1, 1, 130, launch_stream<1>},
+    {0, 1, 1, 46, launch_stream<0, 3, true, true>},
+    {0, 1, 1, 146, launch_stream<1, 3, true, true>},
+    {0, 1, 1, 246, launch_stream<2, 3, true, true>},
+    {0, 1, 1, 446, launch_stream<4, 3, true, true>},
+    {0, 1, 1, 646, launch_stream<6, 3, true, true>},
+    {0, 1, 1, 438, launch_stream<4, 3, true>}, {0, 1, 1, 838, launch_stream<8, 3, true>},
+    {0, 1, 1, 1238, launch_stream<12, 3, true>},
     // SH kernel: no flow probe (160); every partial last chunk from HBM after
     // the stream (264); no count-index store (1064: counts wrong); the count
     // index stored before the verdict (2064)
     {0, 1, 1, 160, launch_sh<1>}, {0, 1, 1, 264, launch_sh<2, 4>},
     {0, 1, 1, 1064, launch_sh<16, 4>}, {0, 1, 1, 2064, launch_sh<32, 4>},
     // 167: 67 without the flow probe
-    {0, 1, 1, 167, launch_sh<1, 4, SH_MAPC, false, 2>},
+    {0, 1, 1, 167, launch_sh<1, 4, false, 2>},
     // pipe 67 without the count-index store (1667) / the verdict store (6467)
-    {0, 1, 1, 1667, launch_sh<16, 4, SH_MAPC, false, 2>},
-    {0, 1, 1, 6467, launch_sh<64, 4, SH_MAPC, false, 2>},
+    {0, 1, 1, 1667, launch_sh<16, 4, false, 2>},
+    {0, 1, 1, 6467, launch_sh<64, 4, false, 2>},
     // ---- the wave-contiguous shape (WC kernel): F frames per wave trip, NL
     // loads per lane; 80 / 81: F = 2, NL = 3 (1.5-KiB slots) with / without
     // the next trip's span in flight; 82 / 83: F = 4, NL = 6
@@ -3356,8 +3212,7 @@ const char *rx_variant_kernel(uint32_t g, uint32_t pipe) {
     if (g >= 4) return "rx_classify_kernel";
     if (pipe == 20) return "rx_bin_kernel+rx_classify_lane_kernel+rx_classify_kernel";
     switch (pipe % 1000u % 100u) {
-    case 60: case 61: case 62: case 63: case 64: case 65: case 66: case 67: case 68: case 69:
-    case 70: case 71: case 72: case 73: case 74: case 75: case 76: case 77: case 78:
+    case 60: case 64: case 65: case 66: case 67: case 68: case 75:
         return "rx_classify_sh_kernel";
     case 80: case 81: case 82: case 83:
         return "rx_classify_wc_kernel";

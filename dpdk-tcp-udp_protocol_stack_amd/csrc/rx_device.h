@@ -112,22 +112,15 @@ __device__ __forceinline__ void rx_dma16(const void *src, uint32_t lds) {
                  : "memory");
 }
 
-// the streamed 16-B outputs (verdicts, count indices).  RX_ST_POLICY 0: nt
-// stores, which KEEP the written line in the XCD's L2; 1: sc1 (write-through)
-// stores, which drop it (MI355X_MICROARCH.md, store flavours), so hundreds of
-// MB of verdicts per burst do not evict the flow tables the probes read
-#ifndef RX_ST_POLICY
-#define RX_ST_POLICY 0
-#endif
+// the streamed 16-B outputs (verdicts, count indices): nt stores, which KEEP
+// the written line in the XCD's L2
 __device__ __forceinline__ void st_stream16(rx_u32x4 *p, rx_u32x4 w) {
-#if RX_ST_POLICY == 1
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 0" ::"v"(p), "v"(w) : "memory");
-#else
     __builtin_nontemporal_store(w, p);
-#endif
 }
 
-// a write-through 16-B store (sc1) whatever RX_ST_POLICY says.  The s_nop is
+// a write-through 16-B store (sc1), which drops the line from the L2
+// (MI355X_MICROARCH.md, store flavours), so hundreds of MB of verdicts per
+// burst do not evict the flow tables the probes read.  The s_nop is
 // the one wait state a store of more than 8 bytes needs before a VALU may
 // overwrite its data registers: the compiler inserts it after its own stores,
 // but cannot see inside inline asm

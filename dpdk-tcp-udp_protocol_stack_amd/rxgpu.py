@@ -45,11 +45,9 @@ RC_OK, RC_TCP_BAD_CKSUM, RC_TCP_NO_TCB, RC_UDP_NOMEM, RC_UDP_NO_SOCKET, RC_KNI =
 F_TRUNC, F_TCP_NEGLEN, F_UDP_SHORT = 0x1, 0x2, 0x4
 TCP_STATUS_LISTEN, TCP_STATUS_ESTABLISHED = 1, 4
 HOST_ONLY = -1
-# (lanes per frame, passes up front, frames per group, pipeline) compiled in
-# rx_classify.hip (verdict-exact ones; the >= 100 pipeline ids are ablations)
 # the product library's classify variants (csrc/rx_classify.hip k_variants):
-# (lanes per frame, passes, frames per group, pipeline); every one gives the
-# reference's verdicts (tests/test_gpu_parity.py runs each)
+# (lanes per frame, passes up front, frames per group, pipeline); every one
+# gives the reference's verdicts (tests/test_gpu_parity.py runs each)
 KERNEL_VARIANTS = [(1, 4, 1, 12), (1, 4, 1, 5), (1, 4, 1, 14), (1, 4, 1, 19), (1, 4, 1, 25), (1, 4, 1, 16),
                    (1, 4, 1, 0),
                    (4, 1, 1, 1), (8, 2, 2, 0), (8, 2, 2, 40), (8, 2, 2, 41), (8, 2, 2, 42), (8, 2, 2, 48),
