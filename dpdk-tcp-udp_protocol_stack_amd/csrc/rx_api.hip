@@ -39,6 +39,12 @@ hipError_t tx_cksum_launch(uint8_t *pkts, const uint32_t *off, const uint16_t *l
                            uint32_t unit_log2, uint32_t len_hint, uint32_t variant,
                            uint32_t bpc_cap, hipStream_t s);
 uint32_t tx_num_variants();
+hipError_t tx_encode_launch(const void *txd, uint32_t n, const uint8_t *pay, uint8_t *pkts,
+                            uint64_t cap, uint32_t slot, uint32_t *off, uint16_t *len,
+                            uint32_t len_hint, uint32_t flags, uint32_t *totals, void *ws,
+                            uint32_t variant, uint32_t bpc_cap, hipStream_t s);
+uint32_t txe_num_variants();
+size_t txe_ws_bytes(uint32_t n);
 size_t rx_split_ws_bytes(uint32_t n, uint32_t nsh);
 hipError_t rx_split_launch(const uint8_t *pkts, const uint32_t *off, const uint16_t *len,
                            uint32_t n, uint32_t unit_log2, uint32_t nsh, uint32_t *first,
@@ -188,6 +194,9 @@ struct rxg_ctx {
     uint32_t tune_g = 0, tune_p = 0, tune_fpg = 0, tune_pipe = ~0u; // rxg_tune override
     uint32_t tune_bpc = 0; // rxg_tune_grid: resident blocks per CU cap (0 = occupancy)
     uint32_t tune_tx = RXG_TX_AUTO, tune_tx_bpc = 0; // rxg_tune_tx
+    uint32_t tune_txe = RXG_TX_AUTO, tune_txe_bpc = 0; // rxg_tune_txe
+    void *d_txe = nullptr; // rxg_tx_encode's device staging, grown on demand
+    size_t d_txe_cap = 0;
     // launch workspace, grown on demand: [binned lists][count indices x 2][count
     // slabs].  Three regions are tracked, each by the event of its last use and
     // that use's stream: index buffer 0 (with the lists), index buffer 1, the
@@ -735,6 +744,7 @@ void rxg_close(rxg_ctx *c) {
     (void)hipFree(c->d_counts_base);
     (void)hipFree(c->d_ws);
     (void)hipFree(c->d_aux);
+    (void)hipFree(c->d_txe);
     (void)hipFree(c->d_cp_dg);
     (void)hipFree(c->d_cp_first);
     (void)hipFree(c->d_cp_payload);
@@ -1119,6 +1129,14 @@ int rxg_tune_tx(rxg_ctx *c, uint32_t variant, uint32_t blocks_per_cu) {
         return RXG_EINVAL;
     c->tune_tx = variant;
     c->tune_tx_bpc = blocks_per_cu;
+    return RXG_OK;
+}
+
+int rxg_tune_txe(rxg_ctx *c, uint32_t variant, uint32_t blocks_per_cu) {
+    if (!c || blocks_per_cu > 32 || (variant != RXG_TX_AUTO && variant >= txe_num_variants()))
+        return RXG_EINVAL;
+    c->tune_txe = variant;
+    c->tune_txe_bpc = blocks_per_cu;
     return RXG_OK;
 }
 
@@ -2040,6 +2058,90 @@ int rxg_gather_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off,
     if (span) *span = units << 6;
     if ((units << 6) > dst_cap || units > 0xFFFFFFFFull) return RXG_ERANGE;
     return RXG_OK;
+}
+
+// K5: the layout pass (in d_aux) and the encoder on `stream`
+int rxg_tx_encode_dev(rxg_ctx *c, const rxg_txd *d_txd, uint32_t n, const uint8_t *d_payload,
+                      uint8_t *d_pkts, uint64_t cap_bytes, uint32_t slot_bytes, uint32_t *d_off,
+                      uint16_t *d_len, uint32_t len_hint, uint32_t flags, uint32_t *d_totals,
+                      void *stream) {
+    if (!c) return RXG_EINVAL;
+    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
+    if (slot_bytes & 63u) return RXG_EINVAL;
+    if (!d_totals) return RXG_EINVAL;
+    if (n && (!d_txd || !d_pkts || !d_off || !d_len)) return RXG_EINVAL;
+    if (((uintptr_t)d_txd | (uintptr_t)d_payload | (uintptr_t)d_pkts) & 15u) return RXG_EINVAL;
+    DEVGUARD(c);
+    const hipStream_t s = (hipStream_t)stream;
+    if (n == 0) {
+        HIPCHK(hipMemsetAsync(d_totals, 0, 16, s));
+        return RXG_OK;
+    }
+    int rc = aux_begin(c, txe_ws_bytes(n), s);
+    if (rc) return rc;
+    HIPCHK(tx_encode_launch(d_txd, n, d_payload, d_pkts, cap_bytes, slot_bytes, d_off, d_len,
+                            len_hint, flags, d_totals, c->d_aux, c->tune_txe, c->tune_txe_bpc, s));
+    return aux_end(c, s);
+}
+
+// descriptors and payloads up, K5, frames with off / len back; all on the
+// context's stream, through one staging buffer:
+// [txd][payload, to its 16-B end][off][len][totals][frames]
+int rxg_tx_encode(rxg_ctx *c, const rxg_txd *txd, uint32_t n, const uint8_t *payload,
+                  uint64_t payload_bytes, uint8_t *pkts, uint64_t cap_bytes, uint32_t *off,
+                  uint16_t *len, uint32_t flags, uint64_t *span) {
+    if (!c) return RXG_EINVAL;
+    if (span) *span = 0;
+    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
+    if (n == 0) return RXG_OK;
+    if (!txd || !pkts || !off || !len) return RXG_EINVAL;
+    uint64_t need = 0, pay_end = 0; // frame bytes if nothing is skipped; payload bytes read
+    for (uint32_t k = 0; k < n; ++k) {
+        const rxg_txd &d = txd[k];
+        uint64_t fl = d.kind == RXG_TXD_UDP   ? 42ull + d.pay_len
+                      : d.kind == RXG_TXD_TCP ? 54ull + 4ull * d.optlen + d.pay_len
+                      : d.kind == RXG_TXD_ARP ? 42ull
+                                              : 0ull;
+        if (fl == 0 || fl > 65535u) continue;
+        need += (fl + 63u) & ~63ull;
+        if (d.kind == RXG_TXD_ARP || d.pay_len == 0) continue;
+        const uint64_t e = (uint64_t)d.pay_off16 * 16 + d.pay_len;
+        if (!payload || e > payload_bytes) return RXG_EINVAL;
+        if (e > pay_end) pay_end = e;
+    }
+    if (need > cap_bytes) need = cap_bytes;
+    DEVGUARD(c);
+    const size_t o_pay = (size_t)n * sizeof(rxg_txd);
+    const size_t o_off = o_pay + ((pay_end + 15u) & ~(size_t)15u);
+    const size_t o_len = o_off + (((size_t)n * 4 + 15u) & ~(size_t)15u);
+    const size_t o_tot = o_len + (((size_t)n * 2 + 15u) & ~(size_t)15u);
+    const size_t o_pkt = (o_tot + 16 + 63u) & ~(size_t)63u;
+    const hipStream_t s = c->stream;
+    int rc = ensure_dev_async(&c->d_txe, &c->d_txe_cap, o_pkt + need + 64, s);
+    if (rc) return rc;
+    uint8_t *d = reinterpret_cast<uint8_t *>(c->d_txe);
+    HIPCHK(hipMemcpyAsync(d, txd, o_pay, hipMemcpyHostToDevice, s));
+    if (pay_end) {
+        // (the tail of the last 16-B chunk is read by the kernel and masked)
+        HIPCHK(hipMemsetAsync(d + o_off - 16, 0, 16, s));
+        HIPCHK(hipMemcpyAsync(d + o_pay, payload, pay_end, hipMemcpyHostToDevice, s));
+    }
+    rc = rxg_tx_encode_dev(c, reinterpret_cast<const rxg_txd *>(d), n, d + o_pay, d + o_pkt,
+                           need, 0, // (= cap_bytes where it binds)
+                           reinterpret_cast<uint32_t *>(d + o_off),
+                           reinterpret_cast<uint16_t *>(d + o_len), (uint32_t)(need / n), flags,
+                           reinterpret_cast<uint32_t *>(d + o_tot), s);
+    if (rc) return rc;
+    uint32_t tot[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(tot, d + o_tot, 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(off, d + o_off, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(len, d + o_len, (size_t)n * 2, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const uint64_t used = ((uint64_t)tot[2] << 32) | tot[1];
+    if (used > need) return RXG_EHIP; // (cannot happen: the kernel's own capacity rule)
+    if (used) HIPCHK(hipMemcpy(pkts, d + o_pkt, used, hipMemcpyDeviceToHost));
+    if (span) *span = used;
+    return tot[3] ? RXG_ERANGE : RXG_OK;
 }
 
 // the increment since the last call is all-reduced and folded into the

@@ -1,0 +1,180 @@
+// tx_encode_host.cpp — rxg_tx_encode_host: the TX encoder (K5, tx_encode.hip)
+// restated in plain C++ for callers without a GPU and as the tests' reference.
+// Host only: no HIP, no context.  The frames are those of the reference's
+// encoders with both checksums filled:
+//   ng_encode_udp_apppkt  udp.c:59-98      ng_encode_tcp_apppkt  tcp.c:420-466
+//   ng_encode_arp_pkt     common.c:206-241
+//   rte_ipv4_cksum rte_ip.h:255-265, rte_ipv4_udptcp_cksum :325-349 (DPDK 19.11.12)
+#include <stdint.h>
+#include <string.h>
+
+#include "../../include/rxgpu.h"
+
+static_assert(sizeof(rxg_txd) == 48, "rxg_txd is 48 bytes");
+
+namespace {
+
+inline void wr16be(uint8_t *p, uint32_t v) {
+    p[0] = (uint8_t)(v >> 8);
+    p[1] = (uint8_t)v;
+}
+inline void wr32be(uint8_t *p, uint32_t v) {
+    p[0] = (uint8_t)(v >> 24);
+    p[1] = (uint8_t)(v >> 16);
+    p[2] = (uint8_t)(v >> 8);
+    p[3] = (uint8_t)v;
+}
+inline uint64_t align64(uint64_t x) { return (x + 63u) & ~63ull; }
+
+// frame length of a descriptor; 0 = skipped (unknown kind, or longer than a
+// frame length can say)
+uint32_t frame_len(const rxg_txd &d) {
+    uint64_t fl = 0;
+    if (d.kind == RXG_TXD_UDP) fl = 42ull + d.pay_len;
+    else if (d.kind == RXG_TXD_TCP) fl = 54ull + 4ull * d.optlen + d.pay_len;
+    else if (d.kind == RXG_TXD_ARP) fl = 42;
+    return fl > 65535u ? 0u : (uint32_t)fl;
+}
+
+// __rte_raw_cksum over [p, p + n): 16-bit words as they lie in memory, an odd
+// last byte as the low half of a word
+uint32_t raw_sum(const uint8_t *p, uint32_t n, uint32_t s) {
+    uint32_t i = 0;
+    for (; i + 1 < n; i += 2) s += (uint32_t)p[i] | ((uint32_t)p[i + 1] << 8);
+    if (i < n) s += p[i];
+    return s;
+}
+uint32_t fold16(uint32_t s) {
+    s = (s >> 16) + (s & 0xFFFFu);
+    s = (s >> 16) + (s & 0xFFFFu);
+    return s;
+}
+
+// the frame of d (fl bytes) at m, both checksum fields 0
+void encode(uint8_t *m, const rxg_txd &d, uint32_t fl, const uint8_t *pay) {
+    static const uint8_t ones[6] = {0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF};
+    if (d.kind == RXG_TXD_ARP) { // common.c:206-241
+        if (memcmp(d.dst_mac, ones, 6)) memcpy(m, d.dst_mac, 6);
+        else memset(m, 0, 6);
+        memcpy(m + 6, d.src_mac, 6);
+        wr16be(m + 12, 0x0806);
+        wr16be(m + 14, 1);
+        wr16be(m + 16, 0x0800);
+        m[18] = 6;
+        m[19] = 4;
+        wr16be(m + 20, 1);
+        memcpy(m + 22, d.src_mac, 6);
+        memcpy(m + 28, &d.sip, 4);
+        memcpy(m + 32, d.dst_mac, 6);
+        memcpy(m + 38, &d.dip, 4);
+        return;
+    }
+    const bool tcp = d.kind == RXG_TXD_TCP;
+    memcpy(m, d.dst_mac, 6);
+    memcpy(m + 6, d.src_mac, 6);
+    wr16be(m + 12, 0x0800);
+    uint8_t *ip = m + 14; // udp.c:74-85, tcp.c:434-445
+    ip[0] = 0x45;
+    ip[1] = 0;
+    wr16be(ip + 2, fl - 14);
+    memset(ip + 4, 0, 4);
+    ip[8] = 64;
+    ip[9] = tcp ? 6 : 17;
+    ip[10] = ip[11] = 0;
+    memcpy(ip + 12, &d.sip, 4);
+    memcpy(ip + 16, &d.dip, 4);
+    uint8_t *t = m + 34;
+    memcpy(t, &d.sport, 2);
+    memcpy(t + 2, &d.dport, 2);
+    uint32_t hdr = 42;
+    if (tcp) { // tcp.c:446-463
+        wr32be(t + 4, d.seq);
+        wr32be(t + 8, d.ack);
+        t[12] = d.hdrlen_off;
+        t[13] = d.tcp_flags;
+        memcpy(t + 14, &d.window, 2);
+        t[16] = t[17] = 0;
+        memcpy(t + 18, &d.urp, 2);
+        memset(t + 20, 0, 4u * d.optlen);
+        hdr = 54u + 4u * d.optlen;
+    } else { // udp.c:86-95
+        wr16be(t + 4, fl - 34);
+        t[6] = t[7] = 0;
+    }
+    if (fl > hdr) memcpy(m + hdr, pay, fl - hdr);
+}
+
+void fill_cksums(uint8_t *m, uint32_t fl, bool tcp) {
+    const uint32_t kip = fold16(raw_sum(m + 14, 20, 0));
+    const uint16_t hip = (uint16_t)(kip == 0xFFFFu ? kip : ~kip);
+    const uint32_t l4n = fl - 34;
+    // pseudo-header: sip, dip, {0, proto}, be16(l4 length)
+    uint32_t s = raw_sum(m + 26, 8, 0) + ((tcp ? 6u : 17u) << 8) +
+                 (((l4n & 0xFFu) << 8) | (l4n >> 8));
+    s = raw_sum(m + 34, l4n, s);
+    uint16_t k = (uint16_t)~fold16(s);
+    if (k == 0 && !tcp) k = 0xFFFF;
+    memcpy(m + 24, &hip, 2);
+    memcpy(m + (tcp ? 50 : 40), &k, 2);
+}
+
+} // namespace
+
+extern "C" int rxg_tx_encode_host(const rxg_txd *txd, uint32_t n, const uint8_t *payload,
+                                  uint64_t payload_bytes, uint8_t *pkts, uint64_t cap_bytes,
+                                  uint32_t slot_bytes, uint32_t *off, uint16_t *len,
+                                  uint32_t flags, uint64_t *span, uint32_t totals[4]) {
+    if (span) *span = 0;
+    if (totals) memset(totals, 0, 16);
+    if (slot_bytes & 63u) return RXG_EINVAL;
+    if (n == 0) return RXG_OK;
+    if (!txd || !pkts || !off || !len) return RXG_EINVAL;
+    for (uint32_t k = 0; k < n; ++k) { // every payload inside the payload buffer
+        const uint32_t fl = frame_len(txd[k]);
+        if (!fl || txd[k].kind == RXG_TXD_ARP || !txd[k].pay_len) continue;
+        if (!payload || (uint64_t)txd[k].pay_off16 * 16 + txd[k].pay_len > payload_bytes)
+            return RXG_EINVAL;
+    }
+    const uint64_t lim = 64ull << 32; // offsets are 32 bits of 64-B units
+    const uint64_t cap = cap_bytes < lim ? cap_bytes : lim;
+    uint64_t pos = 0, end = 0;
+    uint32_t written = 0, skipped = 0;
+    bool full = false;
+    for (uint32_t k = 0; k < n; ++k) {
+        const rxg_txd &d = txd[k];
+        uint32_t fl = frame_len(d);
+        if (slot_bytes && fl > slot_bytes) fl = 0;
+        const uint64_t at = slot_bytes ? (uint64_t)k * slot_bytes : pos;
+        const uint64_t room = slot_bytes ? slot_bytes : align64(fl);
+        bool ok = fl != 0;
+        if (ok && slot_bytes == 0) {
+            if (full || at + room > cap) ok = false, full = true;
+        } else if (ok && at + room > cap) {
+            ok = false;
+        }
+        if (!ok) {
+            off[k] = 0;
+            len[k] = 0;
+            ++skipped;
+            continue;
+        }
+        uint8_t *m = pkts + at;
+        encode(m, d, fl, payload ? payload + (uint64_t)d.pay_off16 * 16 : nullptr);
+        if (d.kind != RXG_TXD_ARP && !(flags & RXG_TXE_NO_CKSUM))
+            fill_cksums(m, fl, d.kind == RXG_TXD_TCP);
+        memset(m + fl, 0, align64(fl) - fl);
+        off[k] = (uint32_t)(at >> 6);
+        len[k] = (uint16_t)fl;
+        end = at + align64(fl);
+        if (slot_bytes == 0) pos = end;
+        ++written;
+    }
+    if (span) *span = end;
+    if (totals) {
+        totals[0] = written;
+        totals[1] = (uint32_t)end;
+        totals[2] = (uint32_t)(end >> 32);
+        totals[3] = skipped;
+    }
+    return skipped ? RXG_ERANGE : RXG_OK;
+}

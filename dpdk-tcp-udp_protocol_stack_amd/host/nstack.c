@@ -861,6 +861,11 @@ static void restate_tcb(struct tcp_stream *s, int lookup_moves) {
     g_dirty = 1;
 }
 
+/* the GPU TX encoder's state (defined with nstack_tx_burst) */
+static int g_tx_encode;
+static atomic_ullong g_txe_frames;
+static void tx_stage_free(void);
+
 /* ---- lifecycle ---------------------------------------------------------- */
 int nstack_init(int device, uint32_t max_burst, uint64_t max_bytes) {
     pthread_mutex_lock(&g_lock);
@@ -933,6 +938,9 @@ void nstack_fini(void) {
     memset(g_local_mac, 0, sizeof(g_local_mac));
     reclaim(); /* (what the blocks' last puts let go of) */
     g_inplace = 0; /* (options last one stack) */
+    g_tx_encode = 0;
+    atomic_store_explicit(&g_txe_frames, 0, memory_order_relaxed);
+    tx_stage_free();
     g_mb_release = NULL;
     g_mb_arg = NULL;
     if (g_ctx) rxg_close(g_ctx);
@@ -2893,6 +2901,81 @@ int nstack_arp_insert(uint32_t ip, const uint8_t mac[6]) {
     return r;
 }
 
+/* ---- TX through the GPU encoder (K5, nstack_set_tx_encode): the walks of
+ * nstack_tx_burst fill send descriptors instead of frames, the payloads go
+ * into a staging buffer (pinned through rxg_register_host where the context
+ * has a device) at 16-B aligned offsets, and one rxg_tx_encode call writes the
+ * burst.  Used by the protocol thread only. */
+static int g_tx_encode;
+static atomic_ullong g_txe_frames; /* stat 13 */
+static rxg_txd *s_txd;
+static uint32_t s_txd_cap;
+static uint8_t *s_txpay;
+static uint64_t s_txpay_cap, s_txpay_len;
+
+int nstack_set_tx_encode(int on) {
+    pthread_mutex_lock(&g_lock);
+    g_tx_encode = on != 0;
+    pthread_mutex_unlock(&g_lock);
+    return 0;
+}
+
+static void tx_stage_free(void) {
+    if (s_txpay && g_ctx) (void)rxg_unregister_host(g_ctx, s_txpay);
+    free(s_txpay), free(s_txd);
+    s_txpay = NULL, s_txd = NULL;
+    s_txpay_cap = s_txpay_len = 0;
+    s_txd_cap = 0;
+}
+
+/* room for `bytes` more staged payload bytes (to their 16-B end); 0 = no memory */
+static int tx_stage_room(uint64_t bytes) {
+    const uint64_t need = s_txpay_len + ((bytes + 15u) & ~15ull);
+    if (need <= s_txpay_cap) return 1;
+    uint64_t cap = s_txpay_cap ? s_txpay_cap : 1u << 16;
+    while (cap < need) cap *= 2;
+    void *p = NULL;
+    if (posix_memalign(&p, 4096, cap)) return 0;
+    if (s_txpay_len) memcpy(p, s_txpay, s_txpay_len);
+    if (s_txpay && g_ctx) (void)rxg_unregister_host(g_ctx, s_txpay);
+    free(s_txpay);
+    s_txpay = p;
+    s_txpay_cap = cap;
+    if (g_ctx) (void)rxg_register_host(g_ctx, p, cap); /* pinned where there is a device */
+    return 1;
+}
+
+/* descriptor k of the burst: its payload staged (the caller has made room),
+ * the position advanced as tx_place does; kind RXG_TXD_ARP: ng_send_arp's
+ * request for dip (enc_arp) */
+static void tx_describe(uint32_t kind, const uint8_t *src_mac, const uint8_t *dst_mac, uint32_t sip,
+                        uint32_t dip, const struct tcp_fragment *f, uint16_t sport, uint16_t dport,
+                        const uint8_t *data, uint32_t length, uint32_t fl, uint64_t *pos,
+                        uint32_t *n) {
+    rxg_txd *d = &s_txd[*n];
+    memset(d, 0, sizeof(*d));
+    memcpy(d->dst_mac, dst_mac, 6);
+    memcpy(d->src_mac, src_mac, 6);
+    d->sip = sip, d->dip = dip;
+    d->sport = sport, d->dport = dport;
+    d->kind = (uint8_t)kind;
+    if (f) {
+        d->seq = f->seqnum, d->ack = f->acknum;
+        d->window = f->windows, d->urp = f->tcp_urp;
+        d->hdrlen_off = f->hdrlen_off, d->tcp_flags = f->tcp_flags;
+        d->optlen = (uint8_t)f->optlen;
+    }
+    d->pay_off16 = (uint32_t)(s_txpay_len >> 4);
+    d->pay_len = length;
+    if (length) {
+        if (data) memcpy(s_txpay + s_txpay_len, data, length);
+        else memset(s_txpay + s_txpay_len, 0, length);
+        s_txpay_len += ((uint64_t)length + 15u) & ~15ull;
+    }
+    *pos += align64(fl);
+    ++*n;
+}
+
 /* frame k of the burst: zero fill to the 64-B slot end, descriptor */
 static void tx_place(uint8_t *fp, uint32_t fl, uint64_t *pos, uint32_t *off, uint16_t *len,
                      uint32_t *n) {
@@ -2912,6 +2995,19 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
     uint32_t n = 0;
     uint64_t pos = 0;
     int full = 0;
+    /* the GPU encoder: descriptors instead of frames (same walks, same rules) */
+    int enc = g_tx_encode && cksum && max_frames;
+    if (enc) {
+        s_txpay_len = 0;
+        if (s_txd_cap < max_frames) {
+            rxg_txd *t = realloc(s_txd, (size_t)max_frames * sizeof(*t));
+            if (!t) {
+                pthread_mutex_unlock(&g_lock);
+                return RXG_ENOMEM;
+            }
+            s_txd = t, s_txd_cap = max_frames;
+        }
+    }
     /* udp_out, udp.c:123-164: at most one datagram per socket, list order */
     for (struct localhost *h = g_pstHost; h && n < max_frames && !full; h = h->next) {
         struct offload *o = NULL;
@@ -2930,7 +3026,7 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
             g_stat[1]++;
             continue;
         }
-        if (pos + align64(fl) > cap_bytes) {
+        if (pos + align64(fl) > cap_bytes || (enc && !tx_stage_room(dmac ? o->length : 0))) {
             pthread_mutex_unlock(&h->mutex);
             full = 1;
             break;
@@ -2938,7 +3034,11 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
         ring_dequeue(h->sndbuf, (void **)&o);
         uint8_t *fp = pkts + pos;
         if (!dmac) { /* an ARP request first, the datagram queued again (udp.c:139-146) */
-            enc_arp(fp, k_default_arp_mac, o->sip, o->dip);
+            if (enc)
+                tx_describe(RXG_TXD_ARP, g_local_mac, k_default_arp_mac, o->sip, o->dip, NULL, 0, 0,
+                            NULL, 0, fl, &pos, &n);
+            else
+                enc_arp(fp, k_default_arp_mac, o->sip, o->dip);
             if (ring_enqueue(h->sndbuf, o)) {
                 free(o->data);
                 free(o);
@@ -2947,11 +3047,15 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
             pthread_mutex_unlock(&h->mutex);
         } else {
             pthread_mutex_unlock(&h->mutex);
-            enc_udp(fp, h->localmac, dmac, o);
+            if (enc)
+                tx_describe(RXG_TXD_UDP, h->localmac, dmac, o->sip, o->dip, NULL, o->sport,
+                            o->dport, o->data, o->length, fl, &pos, &n);
+            else
+                enc_udp(fp, h->localmac, dmac, o);
             free(o->data);
             free(o);
         }
-        tx_place(fp, fl, &pos, off, len, &n);
+        if (!enc) tx_place(fp, fl, &pos, off, len, &n);
     }
     /* tcp_out, tcp.c:492-555: at most one fragment per tcb, list order */
     for (struct tcp_stream *s = g_tcb_set; s && n < max_frames && !full; s = s->next) {
@@ -2970,39 +3074,57 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
             continue;
         }
         const uint32_t fl = (uint32_t)fl64;
-        if (pos + align64(fl) > cap_bytes) {
+        if (pos + align64(fl) > cap_bytes || (enc && !tx_stage_room(dmac ? f->length : 0))) {
             pthread_mutex_unlock(&s->mutex);
             full = 1;
             break;
         }
         uint8_t *fp = pkts + pos;
         if (!dmac) { /* tcp.c:522-535: an ARP request, the fragment dequeued and queued again */
-            enc_arp(fp, k_default_arp_mac, s->dip, s->sip);
+            if (enc)
+                tx_describe(RXG_TXD_ARP, g_local_mac, k_default_arp_mac, s->dip, s->sip, NULL, 0, 0,
+                            NULL, 0, fl, &pos, &n);
+            else
+                enc_arp(fp, k_default_arp_mac, s->dip, s->sip);
             struct tcp_fragment *d = tq_detach(s->sndbuf, &s->sq);
             if (d && tq_push(s->sndbuf, &s->sq, d)) {
                 frag_item_free(d);
                 g_stat[1]++;
             }
         } else {
-            enc_tcp(fp, s->localmac, dmac, s->dip, s->sip, f); /* local -> remote (tcp.c:542) */
+            if (enc) /* local -> remote (tcp.c:542) */
+                tx_describe(RXG_TXD_TCP, s->localmac, dmac, s->dip, s->sip, f, f->sport, f->dport,
+                            f->data, f->length, fl, &pos, &n);
+            else
+                enc_tcp(fp, s->localmac, dmac, s->dip, s->sip, f);
             tq_pop(s->sndbuf, &s->sq);
         }
         pthread_mutex_unlock(&s->mutex);
-        tx_place(fp, fl, &pos, off, len, &n);
+        if (!enc) tx_place(fp, fl, &pos, off, len, &n);
     }
     rxg_ctx *ctx = g_ctx;
     pthread_mutex_unlock(&g_lock);
     if (span) *span = pos;
     if (cksum && n) {
         if (!ctx) return RXG_EINVAL;
-        int rc = rxg_tx_cksum(ctx, pkts, pos, off, len, n, 6); /* K2 on the GPU */
+        int rc;
+        if (enc) { /* K5 on the GPU: the frames, off and len of the walks' descriptors */
+            uint64_t used = 0;
+            rc = rxg_tx_encode(ctx, s_txd, n, s_txpay, s_txpay_len, pkts, cap_bytes, off, len, 0,
+                               &used);
+            if (rc == RXG_OK && used != pos) rc = RXG_ERANGE;
+            if (rc == RXG_OK) atomic_fetch_add_explicit(&g_txe_frames, n, memory_order_relaxed);
+        } else {
+            rc = rxg_tx_cksum(ctx, pkts, pos, off, len, n, 6); /* K2 on the GPU */
+        }
         if (rc) return rc;
     }
     return (int)n;
 }
 
 uint64_t nstack_stat(int which) {
-    if (which < 0 || which > 12) return 0;
+    if (which < 0 || which > 13) return 0;
+    if (which == 13) return (uint64_t)atomic_load_explicit(&g_txe_frames, memory_order_relaxed);
     if (which == 12) return (uint64_t)atomic_load_explicit(&g_deliveries, memory_order_acquire);
     if (which == 7) return (uint64_t)atomic_load_explicit(&g_pl_batches, memory_order_relaxed);
     if (which >= 8) return (uint64_t)atomic_load_explicit(&g_drain_ns[which - 8], memory_order_relaxed);

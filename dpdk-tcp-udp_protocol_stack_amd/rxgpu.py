@@ -107,6 +107,15 @@ SEGMENT_DTYPE = np.dtype([("frame", "<u4"), ("flow", "<u4"), ("seq", "<u4"), ("a
                           ("plen", "<i4"), ("offset", "<u4"), ("sport", "<u2"), ("dport", "<u2"),
                           ("ncopy", "<u2"), ("flags", "u1"), ("hl", "u1")])
 assert SEGMENT_DTYPE.itemsize == 32
+# rxg_txd, the send descriptor of the TX encoder (K5): sip/dip/sport/dport/
+# window/urp raw as the reference stores them, seq/ack host order
+TXD_DTYPE = np.dtype([("dst_mac", "u1", (6,)), ("src_mac", "u1", (6,)), ("sip", "<u4"), ("dip", "<u4"),
+                      ("sport", "<u2"), ("dport", "<u2"), ("seq", "<u4"), ("ack", "<u4"),
+                      ("window", "<u2"), ("urp", "<u2"), ("hdrlen_off", "u1"), ("tcp_flags", "u1"),
+                      ("optlen", "u1"), ("kind", "u1"), ("pay_off16", "<u4"), ("pay_len", "<u4")])
+assert TXD_DTYPE.itemsize == 48
+TXD_UDP, TXD_TCP, TXD_ARP = 0, 1, 2
+TXE_NO_CKSUM = 0x1
 
 
 class Delivery(C.Structure):
@@ -217,6 +226,13 @@ _pcap_read = _sig("rxg_pcap_read_burst", _i32, _vp, _vp, _u64, _vp, _vp, _u32, _
 _pcap_write = _sig("rxg_pcap_write", _i32, C.c_char_p, _vp, _vp, _vp, _u32, _u32)
 _tx_cksum_dev = _sig("rxg_tx_cksum_dev", _i32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp)
 _tx_cksum = _sig("rxg_tx_cksum", _i32, _vp, _vp, _u64, _vp, _vp, _u32, _u32)
+_tx_encode_dev = _sig("rxg_tx_encode_dev", _i32, _vp, _vp, _u32, _vp, _vp, _u64, _u32, _vp, _vp, _u32,
+                      _u32, _vp, _vp)
+_tx_encode = _sig("rxg_tx_encode", _i32, _vp, _vp, _u32, _vp, _u64, _vp, _u64, _vp, _vp, _u32,
+                  C.POINTER(_u64))
+_tx_encode_host = _sig("rxg_tx_encode_host", _i32, _vp, _u32, _vp, _u64, _vp, _u64, _u32, _vp, _vp,
+                       _u32, C.POINTER(_u64), _vp)
+_tune_txe = _sig("rxg_tune_txe", _i32, _vp, _u32, _u32)
 _rss_split = _sig("rxg_rss_split", _i32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp)
 _rss_split_dev = _sig("rxg_rss_split_dev", _i32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp,
                       _vp)
@@ -243,7 +259,8 @@ EXPORTED = ["rxg_open", "rxg_close", "rxg_strerror", "rxg_last_hip_error", "rxg_
             "rxg_counts_reset", "rxg_num_flows", "rxg_tune", "rxg_kernel_variant", "rxg_tune_grid", "rxg_tune_tx", "rxg_tune_flow_load", "rxg_tune_tables", "rxg_ft_lookup_udp", "rxg_ft_lookup_tcp", "rxg_ft_dump",
             "rxg_rss_hash", "rxg_gen_flows", "rxg_gen_host", "rxg_gen_dev", "rxg_submit", "rxg_wait",
             "rxg_pcap_open", "rxg_pcap_close", "rxg_pcap_rewind", "rxg_pcap_read_burst",
-            "rxg_pcap_write", "rxg_tx_cksum_dev", "rxg_tx_cksum", "rxg_rss_split",
+            "rxg_pcap_write", "rxg_tx_cksum_dev", "rxg_tx_cksum", "rxg_tx_encode_dev",
+            "rxg_tx_encode", "rxg_tx_encode_host", "rxg_tune_txe", "rxg_rss_split",
             "rxg_rss_split_dev", "rxg_gather_dev", "rxg_group_id", "rxg_group_open",
             "rxg_group_close", "rxg_group_size", "rxg_counts_allreduce", "rxg_ctx_counts_allreduce"]
 
@@ -549,6 +566,35 @@ class Context:
         _check(_tx_cksum_dev(self._h, p(d_pkts), p(d_off), p(d_len), n, off_unit_log2, len_hint,
                              stream), "rxg_tx_cksum_dev")
 
+    def tune_txe(self, variant: int = TX_AUTO, blocks_per_cu: int = 0):
+        """force a TX encode kernel variant (tx_encode.hip k_txe index; TX_AUTO =
+        chosen from len_hint) and cap its resident blocks per CU (0 = default)"""
+        _check(_tune_txe(self._h, variant, blocks_per_cu), "rxg_tune_txe")
+
+    def tx_encode(self, txd: np.ndarray, payload: np.ndarray, cap_bytes: int, flags: int = 0):
+        """frames of a host descriptor burst, packed (PCIe round trip):
+        (pkts[:span], off, len, rc) with rc 0 or RXG_ERANGE (something was skipped)"""
+        txd = np.ascontiguousarray(txd, TXD_DTYPE)
+        payload = np.ascontiguousarray(payload, np.uint8)
+        n = len(txd)
+        pk = np.zeros(max(cap_bytes, 1), np.uint8)
+        off, ln = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint16)
+        span = _u64()
+        rc = _tx_encode(self._h, _ptr(txd), n, _ptr(payload), len(payload), _ptr(pk), cap_bytes,
+                        _ptr(off), _ptr(ln), flags, C.byref(span))
+        if rc not in (0, -34):
+            _check(rc, "rxg_tx_encode")
+        return pk[:span.value], off[:n], ln[:n], rc
+
+    def tx_encode_dev(self, d_txd, n: int, d_payload, d_pkts, cap_bytes: int, slot_bytes: int,
+                      d_off, d_len, len_hint: int, flags: int, d_totals, stream=None):
+        """frames of a device descriptor burst (torch tensors or raw ints), asynchronous"""
+        def p(x):
+            return x if (x is None or isinstance(x, int)) else x.data_ptr()
+        _check(_tx_encode_dev(self._h, p(d_txd), n, p(d_payload), p(d_pkts), cap_bytes, slot_bytes,
+                              p(d_off), p(d_len), len_hint, flags, p(d_totals), stream),
+               "rxg_tx_encode_dev")
+
     def process_mbufs(self, mbufs) -> np.ndarray:
         arr = (C.POINTER(Mbuf) * len(mbufs))(*[C.pointer(m) for m in mbufs])
         out = np.zeros(len(mbufs), VERDICT_DTYPE)
@@ -634,6 +680,26 @@ def pcap_write(path: str, pkts: np.ndarray, off: np.ndarray, lens: np.ndarray,
     lens = np.ascontiguousarray(lens, np.uint16)
     _check(_pcap_write(path.encode(), _ptr(pkts), _ptr(off), _ptr(lens), len(off), off_unit_log2),
            "rxg_pcap_write")
+
+
+def tx_encode_host(txd: np.ndarray, payload: np.ndarray, cap_bytes: int, slot_bytes: int = 0,
+                   flags: int = 0, fill: int = 0):
+    """rxg_tx_encode_host, the TX encoder on the CPU (no context, no device):
+    (pkts, off, len, span, totals, rc); pkts is the whole cap_bytes buffer,
+    prefilled with `fill`, so a caller can see what was left untouched; rc is 0
+    or RXG_ERANGE (something was skipped), anything else raises"""
+    txd = np.ascontiguousarray(txd, TXD_DTYPE)
+    payload = np.ascontiguousarray(payload, np.uint8)
+    n = len(txd)
+    pk = np.full(cap_bytes, fill, np.uint8)
+    off, ln = np.zeros(n, np.uint32), np.zeros(n, np.uint16)
+    span, tot = _u64(), np.zeros(4, np.uint32)
+    rc = _tx_encode_host(txd.ctypes.data, n, payload.ctypes.data if len(payload) else None,
+                         len(payload), pk.ctypes.data, cap_bytes, slot_bytes, off.ctypes.data,
+                         ln.ctypes.data, flags, C.byref(span), tot.ctypes.data)
+    if rc not in (0, -34):
+        _check(rc, "rxg_tx_encode_host")
+    return pk, off, ln, span.value, tot, rc
 
 
 def rss_hash(sip: int, dip: int, sport: int, dport: int) -> int:
@@ -793,7 +859,8 @@ class NStack:
                    ("nstack_stat", _u64, [_i32]),
                    ("nstack_set_local", _i32, [_u32, _vp]),
                    ("nstack_arp_insert", _i32, [_u32, _vp]),
-                   ("nstack_tx_burst", _i32, [_vp, _u64, _vp, _vp, _u32, _i32, _vp])]
+                   ("nstack_tx_burst", _i32, [_vp, _u64, _vp, _vp, _u32, _i32, _vp]),
+                   ("nstack_set_tx_encode", _i32, [_i32])]
             for name, res, args in sig:
                 f = getattr(lib, name)
                 f.restype, f.argtypes = res, args
@@ -1085,6 +1152,11 @@ class NStack:
 
     def arp_insert(self, ip: str, mac: bytes) -> int:
         return self.lib.nstack_arp_insert(ip_raw(ip), (C.c_uint8 * 6)(*mac))
+
+    def set_tx_encode(self, on: bool = True):
+        """nstack_set_tx_encode: tx_burst(cksum=True) builds its frames on the
+        GPU (K5) from descriptors instead of framing them on the host"""
+        return self.lib.nstack_set_tx_encode(1 if on else 0)
 
     def tx_burst(self, max_frames: int = 256, cap_bytes: int = 1 << 20, cksum: bool = False):
         """one udp_out + tcp_out pass: the frames (bytes) it produced"""

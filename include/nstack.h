@@ -182,6 +182,15 @@ int nstack_arp_insert(uint32_t ip, const uint8_t mac[6]);
  * Returns the number of frames (or a negative RXG_E* code); *span = bytes used. */
 int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *len,
                     uint32_t max_frames, int cksum, uint64_t *span);
+/* on != 0: nstack_tx_burst with cksum != 0 builds its frames on the GPU (K5,
+ * rxg_tx_encode).  The two list walks collect send descriptors (rxg_txd; ARP
+ * requests included) in the same order and with the same requeue, drop and
+ * capacity rules, the payloads go into pinned staging at 16-B aligned
+ * offsets, and one rxg_tx_encode call produces the burst: frames, off, len,
+ * *span, return value and queue state are those of the host-framed path.
+ * Default off; with cksum == 0 the host frames as before.  nstack_stat(13)
+ * counts the frames the encoder produced.  Returns 0. */
+int nstack_set_tx_encode(int on);
 
 /* The application side of a benchmark, in one call: every UDP socket read
  * with nrecvfrom until empty, every tcb's receive queue read (nrecv) and its
@@ -260,7 +269,8 @@ int nstack_set_halves(uint32_t min_half);
  * bursts delivered (nstack_rx_burst, nstack_deliver), read without any lock: a
  * polling application that reads a value it has not seen finds that burst's
  * items in its next nstack_drain_all (bumped with release order after the
- * deliveries, read with acquire).  Counter 1 also counts TX items dropped (a
+ * deliveries, read with acquire); 13 = frames produced by the TX encoder
+ * (nstack_set_tx_encode).  Counter 1 also counts TX items dropped (a
  * send ring full, or a datagram too long for a frame). */
 uint64_t nstack_stat(int which);
 

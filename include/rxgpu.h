@@ -475,6 +475,81 @@ int rxg_tx_cksum_dev(rxg_ctx *ctx, uint8_t *d_pkts, const uint32_t *d_off, const
 int rxg_tx_cksum(rxg_ctx *ctx, uint8_t *pkts, uint64_t span_bytes, const uint32_t *off,
                  const uint16_t *len, uint32_t n, uint32_t off_unit_log2);
 
+/* TX encode (K5, csrc/tx_encode.hip): complete outgoing frames from send
+ * descriptors and payloads, both checksums filled, in one pass.  The frame of
+ * a descriptor is byte for byte what the reference's encoders write:
+ *   RXG_TXD_UDP  ng_encode_udp_apppkt udp.c:59-98     42 + pay_len bytes
+ *   RXG_TXD_TCP  ng_encode_tcp_apppkt tcp.c:420-466   54 + 4*optlen + pay_len
+ *   RXG_TXD_ARP  ng_encode_arp_pkt    common.c:206-241 42 (request, opcode 1)
+ * IPv4 id and fragment fields 0, ttl 64 (udp.c:74-85, tcp.c:434-445); the
+ * IPv4 header checksum (rte_ipv4_cksum, 0xFFFF kept) at offset 24 and the L4
+ * checksum (rte_ipv4_udptcp_cksum, UDP 0 -> 0xFFFF) at 40 / 50 are those
+ * rxg_tx_cksum fills; every frame is zero-filled to its next 64-B boundary.
+ * The descriptor is 48 bytes, 16-B aligned (offsets in the comments). */
+enum { RXG_TXD_UDP = 0, RXG_TXD_TCP = 1, RXG_TXD_ARP = 2 };
+typedef struct rxg_txd {
+    uint8_t dst_mac[6];    /* @0  Ethernet destination; ARP: the target-MAC field (all-ones ->
+                                  Ethernet destination all-zero, common.c:216-223) */
+    uint8_t src_mac[6];    /* @6  (ARP: also the sender MAC) */
+    uint32_t sip, dip;     /* @12 @16 raw network order; ARP: sender / target ip */
+    uint16_t sport, dport; /* @20 @22 raw */
+    uint32_t seq, ack;     /* @24 @28 host order (tcp_fragment.seqnum / acknum; written htonl) */
+    uint16_t window, urp;  /* @32 @34 stored as they are (no htons, tcp.c:454) */
+    uint8_t hdrlen_off;    /* @36 */
+    uint8_t tcp_flags;     /* @37 */
+    uint8_t optlen;        /* @38 option words, written as zeros (tcp.c:420-466) */
+    uint8_t kind;          /* @39 RXG_TXD_* */
+    uint32_t pay_off16;    /* @40 payload start in the payload buffer, 16-B units */
+    uint32_t pay_len;      /* @44 payload bytes (UDP/TCP; ARP: ignored) */
+} rxg_txd;
+
+/* flags: leave both checksum fields 0 (nstack_tx_burst with cksum == 0) */
+#define RXG_TXE_NO_CKSUM 0x1u
+
+/* Device form, asynchronous on `stream`.  d_txd: n descriptors (16-B
+ * aligned); d_payload: the payload buffer (16-B aligned; it extends to the
+ * next 16-B boundary after every payload, the rule frames follow); d_pkts:
+ * cap_bytes of frame memory (64-B aligned).  slot_bytes == 0 packs the
+ * frames: frame k follows frame k-1 at 64-B alignment (a layout pass: tile
+ * sums, a scan, per-tile offsets, as rxg_gather_dev); slot_bytes != 0 (a
+ * multiple of 64) puts frame k at k * slot_bytes.  Outputs: d_off[k] (64-B
+ * units, the layout of nstack_tx_burst and rxg_gather_dev), d_len[k], and
+ * d_totals = {frames written, span bytes low, span bytes high, frames
+ * skipped} (span = end of the last written frame's 64-B slot).  A descriptor
+ * is skipped when its kind is unknown, its frame would exceed 65535 bytes or
+ * slot_bytes, or its slot would pass cap_bytes; it writes nothing and gets
+ * d_off[k] = d_len[k] = 0.  Packed: a descriptor skipped for its kind or
+ * length takes no space; the first frame that would pass cap_bytes ends the
+ * burst (it and every later descriptor are skipped, as nstack_tx_burst stops
+ * at a full buffer).  Bytes outside [slot start, 64-B-rounded frame end) are
+ * never written.  len_hint: typical frame length (0 = unknown), chooses the
+ * kernel variant only.  d_totals is required (n == 0 zeroes it).  Uses the
+ * context's split / gather workspace. */
+int rxg_tx_encode_dev(rxg_ctx *ctx, const rxg_txd *d_txd, uint32_t n, const uint8_t *d_payload,
+                      uint8_t *d_pkts, uint64_t cap_bytes, uint32_t slot_bytes, uint32_t *d_off,
+                      uint16_t *d_len, uint32_t len_hint, uint32_t flags, uint32_t *d_totals,
+                      void *stream);
+/* Host form (packed): descriptors and payloads (payload_bytes: every payload
+ * must end inside it, else RXG_EINVAL) go up, the frames with off / len come
+ * back; synchronous.  *span = bytes of pkts used.  RXG_ERANGE if any
+ * descriptor was skipped (the others are written). */
+int rxg_tx_encode(rxg_ctx *ctx, const rxg_txd *txd, uint32_t n, const uint8_t *payload,
+                  uint64_t payload_bytes, uint8_t *pkts, uint64_t cap_bytes, uint32_t *off,
+                  uint16_t *len, uint32_t flags, uint64_t *span);
+/* The same on the CPU (csrc/tx_encode_host.cpp): no context, no device; the
+ * path for callers without a GPU and the tests' reference, never a fallback
+ * the device calls take.  slot_bytes as rxg_tx_encode_dev (0 = packed);
+ * totals (nullable) as d_totals.  Reads exactly pay_len bytes per payload. */
+int rxg_tx_encode_host(const rxg_txd *txd, uint32_t n, const uint8_t *payload,
+                       uint64_t payload_bytes, uint8_t *pkts, uint64_t cap_bytes,
+                       uint32_t slot_bytes, uint32_t *off, uint16_t *len, uint32_t flags,
+                       uint64_t *span, uint32_t totals[4]);
+
+/* Tuning hook for the TX encode kernel: force entry `variant` of its variant
+ * table (csrc/tx_encode.hip k_txe; RXG_TX_AUTO = chosen from len_hint) and cap
+ * its resident blocks per CU (0 = the variant's default). */
+int rxg_tune_txe(rxg_ctx *ctx, uint32_t variant, uint32_t blocks_per_cu);
+
 /* Tuning hook: force the kernel variant (lanes per frame 1 or 4..64, passes
  * loaded up front, frames per lane group, pipeline mode; 0xFFFFFFFF = the
  * default pipeline); lanes_per_frame = 0 with pipeline 0xFFFFFFFF =
