@@ -25,6 +25,10 @@
 // sits in the first 64-B sector and depends on the whole payload: the first P
 // passes are held in registers and stored after the reduction; longer frames
 // stream their tail chunks out as they are produced, sector 0 goes last.
+//
+// TCP segmentation (rxg_tx_encode_tso_dev) is a sibling of both halves further
+// down: a layout pass over entries and units, and tx_encode_tso_kernel with a
+// lane group per entry.  The kernels above it are not touched by it.
 #include <hip/hip_runtime.h>
 
 #include "rx_common.h"
@@ -292,20 +296,32 @@ struct txe_frame {
     int32_t hc;        // header chunks: output chunk c takes source chunks c - hc, c - hc + 1
     uint32_t k;        // funnel shift (4k + 2 bytes)
     int32_t nb;        // bytes to store: the frame rounded up to 64 (0: skipped)
+    int32_t lo;        // TSO: the segment's first byte in its source chunk 0 (0, 4, 8, 12)
 };
 
-// source chunk a of the payload, bytes outside [0, plen) read as 0 (not loaded)
-template <bool NT>
+// source chunk a of the payload, bytes outside [0, plen) read as 0 (not loaded).
+// TSO: pb is the 16-B chunk that holds the segment's first byte, the segment is
+// the bytes [lo, plen) from there; the bytes below lo in chunk 0 belong to the
+// segment before and read as 0 too (they lie under the header and would be
+// summed into the checksum)
+template <bool NT, bool TSO = false>
 __device__ __forceinline__ uint4 txe_src(const txe_frame &f, int32_t a) {
     uint4 v = make_uint4(0, 0, 0, 0);
     if (a >= 0 && 16 * a < f.plen) {
         v = ldg16<NT>(f.pb + 16 * a);
         if (16 * a + 16 > f.plen) v = chunk_below(v, 16 * a, f.plen);
+        if constexpr (TSO) {
+            if (a == 0) {
+                v.x = f.lo > 0 ? 0u : v.x;
+                v.y = f.lo > 4 ? 0u : v.y;
+                v.z = f.lo > 8 ? 0u : v.z;
+            }
+        }
     }
     return v;
 }
 
-template <int G, int P, int NB>
+template <int G, int P, int NB, bool TSO = false>
 __device__ __forceinline__ void txe_frame_run(const txe_frame &f, uint4 d0, uint4 d1, uint4 d2,
                                               uint32_t kind, uint32_t fl, uint4 (&own)[P],
                                               uint4 (&prv)[NB ? 1 : P], uint32_t gl, uint32_t lane,
@@ -350,8 +366,8 @@ __device__ __forceinline__ void txe_frame_run(const txe_frame &f, uint4 d0, uint
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int32_t a = ((s0 + sb + u * STEP) >> 4) - f.hc + 1;
-            r[u] = txe_src<NB != 0>(f, a);
-            if constexpr (!NB) p[u] = txe_src<false>(f, a - 1);
+            r[u] = txe_src<NB != 0, TSO>(f, a);
+            if constexpr (!NB) p[u] = txe_src<false, TSO>(f, a - 1);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -489,7 +505,418 @@ static const txe_variant k_txe[] = {
     {launch_txe<8, 1, 1, 0>, TXE_FULL_GRID},
 };
 
+// ---- TCP segmentation (rxg_tx_encode_tso_dev) --------------------------------
+// A TCP descriptor longer than mss becomes s frames.  The layout pass scans two
+// quantities, entries (max(1, s)) and 64-B units, and writes off / len per
+// entry, first / nseg per descriptor and the entry -> descriptor map the
+// encoder reads; the encoder is tx_encode_kernel with a lane group per entry.
+// Segment j starts D = j * mss bytes into a 16-B aligned payload; mss % 4 == 0
+// keeps D 4-B aligned, so with every source load still a 16-B aligned chunk
+// (from pb + (D & ~15)) the payload's place in the frame stays 2 mod 4 against
+// the source chunks: the funnel applies with hc / k taken from hdr - (D & 15),
+// and the (D & 15) bytes before the segment in source chunk 0 read as 0.
+
+// how a descriptor is cut, from its third chunk: s segments (0 = skipped), the
+// frame length of every segment but the last, and of the last
+struct txe_cut {
+    unsigned long long s;
+    uint32_t full, last;
+};
+__device__ __forceinline__ txe_cut txe_cut_of(uint4 d2, uint32_t mss, uint32_t slot) {
+    const uint32_t kind = d2.y >> 24, opt = (d2.y >> 16) & 0xFFu, pay = d2.w;
+    txe_cut c;
+    uint64_t full = 0, last = 0;
+    c.s = 1;
+    if (kind == RXG_TXD_TCP && mss) {
+        const uint32_t hdr = 54u + 4u * opt;
+        if (pay) c.s = ((uint64_t)pay + mss - 1) / mss;
+        full = (uint64_t)hdr + (pay < mss ? pay : mss);
+        last = (uint64_t)hdr + (pay - (c.s - 1) * mss);
+    } else {
+        if (kind == RXG_TXD_UDP) full = 42ull + pay;
+        else if (kind == RXG_TXD_TCP) full = 54ull + 4ull * opt + pay;
+        else if (kind == RXG_TXD_ARP) full = 42ull;
+        last = full;
+    }
+    if (full == 0 || full > 65535ull || (slot && full > slot)) c.s = 0;
+    c.full = c.s ? (uint32_t)full : 0u;
+    c.last = c.s ? (uint32_t)last : 0u;
+    return c;
+}
+__device__ __forceinline__ unsigned long long txe_cut_units(const txe_cut &c) {
+    return c.s ? (c.s - 1) * ((c.full + 63u) >> 6) + ((c.last + 63u) >> 6) : 0ull;
+}
+
+struct txe_tso_part {
+    unsigned long long end_units; // end of its last written frame, 64-B units
+    unsigned long long frames, descs; // written
+};
+
+__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long x) {
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+    return x;
+}
+
+// per-chunk sums of the entries (sums_e) and 64-B units (sums_u) of descriptors [0, n)
+__global__ __launch_bounds__(256) void txe_tso_sums_kernel(const uint4 *__restrict__ txd, uint32_t n,
+                                                           uint32_t mss, uint32_t slot,
+                                                           unsigned long long *__restrict__ sums_e,
+                                                           unsigned long long *__restrict__ sums_u) {
+    __shared__ unsigned long long pe[4], pu[4];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t c0 = (uint64_t)blockIdx.x * TXE_CHUNK;
+    unsigned long long se = 0, su = 0;
+    for (uint32_t k = 0; k < TXE_PER_THREAD; ++k) {
+        const uint64_t q = c0 + (uint64_t)k * 256 + tid;
+        if (q < n) {
+            const txe_cut c = txe_cut_of(txd[3 * q + 2], mss, slot);
+            se += c.s ? c.s : 1ull;
+            su += txe_cut_units(c);
+        }
+    }
+    se = wave_sum64(se), su = wave_sum64(su);
+    if ((tid & 63u) == 0) pe[tid >> 6] = se, pu[tid >> 6] = su;
+    __syncthreads();
+    if (tid == 0) {
+        sums_e[blockIdx.x] = pe[0] + pe[1] + pe[2] + pe[3];
+        sums_u[blockIdx.x] = pu[0] + pu[1] + pu[2] + pu[3];
+    }
+}
+
+// txe_scan_kernel over the array v + blockIdx.x * (m + 1), the total left in its
+// slot m: one launch scans the entries and the units
+__global__ __launch_bounds__(1024) void txe_tso_scan_kernel(unsigned long long *__restrict__ v_,
+                                                            uint64_t m) {
+    __shared__ unsigned long long part[1024];
+    unsigned long long *v = v_ + (uint64_t)blockIdx.x * (m + 1);
+    const uint32_t tid = threadIdx.x;
+    const uint64_t per = (m + 1023) / 1024;
+    const uint64_t b = tid * per < m ? tid * per : m, e = b + per < m ? b + per : m;
+    unsigned long long s = 0;
+    for (uint64_t i = b; i < e; ++i) s += v[i];
+    part[tid] = s;
+    __syncthreads();
+    for (uint32_t o = 1; o < 1024; o <<= 1) {
+        const unsigned long long x = tid >= o ? part[tid - o] : 0ull;
+        __syncthreads();
+        part[tid] += x;
+        __syncthreads();
+    }
+    unsigned long long run = part[tid] - s;
+    for (uint64_t i = b; i < e; ++i) {
+        const unsigned long long x = v[i];
+        v[i] = run;
+        run += x;
+    }
+    if (tid == 1023) v[m] = part[1023];
+}
+
+// entries and positions in order inside each chunk.  A descriptor is written
+// iff s > 0, its entries end at or below out_cap and its frames fit the
+// capacity; both limits, once passed, stay passed for every later descriptor
+// that has frames (their scanned positions lie past them).  Per descriptor:
+// first, nseg and (workspace) the packed position of its first frame; the
+// entries are written by txe_tso_entries_kernel, a thread per entry.
+__global__ __launch_bounds__(256) void txe_tso_layout_kernel(
+    const uint4 *__restrict__ txd, uint32_t n, uint32_t mss, uint32_t slot,
+    const unsigned long long *__restrict__ base_e, const unsigned long long *__restrict__ base_u,
+    unsigned long long cap, unsigned long long out_cap,
+    uint32_t *__restrict__ first, uint32_t *__restrict__ nseg, uint32_t *__restrict__ posu,
+    uint32_t nchunks, txe_tso_part *__restrict__ part) {
+    __shared__ unsigned long long run_e, run_u, we[4], wu[4];
+    __shared__ unsigned long long s_end[4], s_fr[4], s_ds[4];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    unsigned long long frames = 0, descs = 0, end = 0;
+    for (uint32_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+        if (tid == 0) run_e = base_e[chunk], run_u = base_u[chunk]; // (read after the first barrier)
+        const uint64_t c0 = (uint64_t)chunk * TXE_CHUNK;
+        for (uint32_t k = 0; k < TXE_PER_THREAD; ++k) {
+            const uint64_t q = c0 + (uint64_t)k * 256 + tid;
+            txe_cut c;
+            c.s = 0, c.full = c.last = 0;
+            if (q < n) c = txe_cut_of(txd[3 * q + 2], mss, slot);
+            const unsigned long long ne = q < n ? (c.s ? c.s : 1ull) : 0ull, u = txe_cut_units(c);
+            unsigned long long xe = ne, xu = u; // inclusive wave scans
+            for (uint32_t o = 1; o < 64; o <<= 1) {
+                const unsigned long long ye = __shfl_up(xe, o), yu = __shfl_up(xu, o);
+                if (lane >= o) xe += ye, xu += yu;
+            }
+            if (lane == 63) we[wv] = xe, wu[wv] = xu;
+            __syncthreads();
+            unsigned long long fe = run_e + xe - ne, pu = run_u + xu - u;
+            for (uint32_t w = 0; w < wv; ++w) fe += we[w], pu += wu[w];
+            if (q < n) {
+                bool ok = c.s != 0 && fe + c.s <= out_cap;
+                if (ok) ok = slot ? (fe + c.s) * slot <= cap : ((pu + u) << 6) <= cap;
+                first[q] = fe > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)fe;
+                nseg[q] = ok ? (uint32_t)c.s : 0u;
+                posu[q] = (uint32_t)pu; // (a written descriptor's frames end below 2^32 units)
+                const unsigned long long fu = (c.full + 63u) >> 6, su = slot >> 6;
+                if (ok) {
+                    const unsigned long long at = slot ? (fe + c.s - 1) * su : pu + (c.s - 1) * fu;
+                    const unsigned long long en = at + ((c.last + 63u) >> 6);
+                    frames += c.s, descs += 1;
+                    if (en > end) end = en;
+                }
+            }
+            __syncthreads();
+            if (tid == 0) {
+                run_e += we[0] + we[1] + we[2] + we[3];
+                run_u += wu[0] + wu[1] + wu[2] + wu[3];
+            }
+            __syncthreads();
+        }
+    }
+    frames = wave_sum64(frames), descs = wave_sum64(descs);
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long y = __shfl_xor(end, o);
+        end = y > end ? y : end;
+    }
+    if (lane == 0) s_end[wv] = end, s_fr[wv] = frames, s_ds[wv] = descs;
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 4; ++w) end = s_end[w] > end ? s_end[w] : end;
+        part[blockIdx.x].end_units = end;
+        part[blockIdx.x].frames = s_fr[0] + s_fr[1] + s_fr[2] + s_fr[3];
+        part[blockIdx.x].descs = s_ds[0] + s_ds[1] + s_ds[2] + s_ds[3];
+    }
+}
+
+// off / len / map of the entries laid out (those below out_cap), a thread per
+// entry: its descriptor is the last one whose first is not above it (first is
+// ascending; a binary search over an array that stays in the caches), the
+// segment number the distance.  The layout loop of a 45-segment descriptor is
+// 45 threads here, not 45 trips of one.
+__global__ __launch_bounds__(256) void txe_tso_entries_kernel(
+    const uint4 *__restrict__ txd, uint32_t n, uint32_t mss, uint32_t slot,
+    const uint32_t *__restrict__ first, const uint32_t *__restrict__ nseg,
+    const uint32_t *__restrict__ posu, const unsigned long long *__restrict__ need,
+    unsigned long long out_cap, uint32_t *__restrict__ off, uint16_t *__restrict__ len,
+    uint32_t *__restrict__ map) {
+    const unsigned long long ne = *need < out_cap ? *need : out_cap;
+    for (unsigned long long e = (unsigned long long)blockIdx.x * 256 + threadIdx.x; e < ne;
+         e += (unsigned long long)gridDim.x * 256) {
+        // first[0] == 0 <= e; descriptor q owns at least one entry, so q <= e
+        uint32_t lo = 0, hi = e < n - 1 ? (uint32_t)e : n - 1;
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo + 1) >> 1);
+            if (first[mid] <= e) lo = mid;
+            else hi = mid - 1;
+        }
+        const uint32_t q = lo, s = nseg[q], j = (uint32_t)e - first[q];
+        uint32_t o = 0, l = 0;
+        if (s) {
+            const uint4 d2 = txd[3 * (uint64_t)q + 2];
+            const uint32_t kind = d2.y >> 24, pay = d2.w;
+            if (kind == RXG_TXD_TCP && mss) {
+                const uint32_t hdr = 54u + 4u * ((d2.y >> 16) & 0xFFu);
+                const uint32_t full = hdr + (pay < mss ? pay : mss);
+                l = j + 1 == s ? hdr + (pay - (s - 1) * mss) : full;
+                o = slot ? (uint32_t)(e * (slot >> 6)) : posu[q] + j * ((full + 63u) >> 6);
+            } else {
+                l = kind == RXG_TXD_TCP ? 54u + 4u * ((d2.y >> 16) & 0xFFu) + pay
+                                        : (kind == RXG_TXD_UDP ? 42u + pay : 42u);
+                o = slot ? (uint32_t)(e * (slot >> 6)) : posu[q];
+            }
+        }
+        map[e] = q;
+        off[e] = o;
+        len[e] = (uint16_t)l;
+    }
+}
+
+// d_totals = {frames written, span bytes low, high, descriptors skipped,
+// entries needed low, high, 0, 0}; one block
+__global__ __launch_bounds__(256) void txe_tso_totals_kernel(const txe_tso_part *__restrict__ part,
+                                                             uint32_t nparts, uint32_t n,
+                                                             const unsigned long long *__restrict__ need,
+                                                             uint32_t *__restrict__ totals) {
+    __shared__ unsigned long long s_end[4], s_fr[4], s_ds[4];
+    unsigned long long end = 0, fr = 0, ds = 0;
+    for (uint32_t i = threadIdx.x; i < nparts; i += 256) {
+        end = part[i].end_units > end ? part[i].end_units : end;
+        fr += part[i].frames, ds += part[i].descs;
+    }
+    fr = wave_sum64(fr), ds = wave_sum64(ds);
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long y = __shfl_xor(end, o);
+        end = y > end ? y : end;
+    }
+    if ((threadIdx.x & 63u) == 0)
+        s_end[threadIdx.x >> 6] = end, s_fr[threadIdx.x >> 6] = fr, s_ds[threadIdx.x >> 6] = ds;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) end = s_end[w] > end ? s_end[w] : end;
+        totals[0] = (uint32_t)(s_fr[0] + s_fr[1] + s_fr[2] + s_fr[3]);
+        totals[1] = (uint32_t)(end << 6);
+        totals[2] = (uint32_t)(end >> 26);
+        totals[3] = n - (uint32_t)(s_ds[0] + s_ds[1] + s_ds[2] + s_ds[3]);
+        totals[4] = (uint32_t)*need;
+        totals[5] = (uint32_t)(*need >> 32);
+        totals[6] = totals[7] = 0u;
+    }
+}
+
+// tx_encode_kernel with a lane group per entry: the descriptor is map[e], the
+// segment e - first[map[e]]; seq and the flag mask go into the descriptor's
+// registers before the header chunk is built from them
+template <int G, int P, int FPG, int NB>
+__global__ __launch_bounds__(256) void tx_encode_tso_kernel(
+    const uint4 *__restrict__ txd, const uint8_t *__restrict__ pay, uint8_t *__restrict__ pkts,
+    const uint32_t *__restrict__ off, const uint16_t *__restrict__ len,
+    const uint32_t *__restrict__ map, const uint32_t *__restrict__ first,
+    const unsigned long long *__restrict__ need, unsigned long long out_cap, uint32_t mss,
+    uint32_t flags) {
+    constexpr uint32_t GPB = 256 / G, TILE = GPB * FPG;
+    constexpr int32_t STEP = 16 * G;
+    const uint32_t tid = threadIdx.x, gl = tid & (G - 1), grp = tid / G, lane = tid & 63u;
+    const int32_t s0 = 16 * (int32_t)gl;
+    const unsigned long long ne = *need < out_cap ? *need : out_cap; // entries laid out
+    for (uint64_t tile = blockIdx.x; tile * TILE < ne; tile += gridDim.x) {
+        txe_frame f[FPG];
+        uint4 d0[FPG], d1[FPG], d2[FPG];
+        uint32_t kind[FPG], fl[FPG];
+        uint4 own[FPG][P], prv[FPG][NB ? 1 : P];
+#pragma unroll
+        for (int i = 0; i < FPG; ++i) {
+            const uint64_t pos = tile * TILE + (uint64_t)i * GPB + grp;
+            const uint64_t e = pos < ne ? pos : 0;
+            fl[i] = pos < ne ? (uint32_t)len[e] : 0u;
+            const uint64_t q = map[e];
+            const uint32_t j = (uint32_t)e - first[q];
+            d0[i] = txd[3 * q], d1[i] = txd[3 * q + 1], d2[i] = txd[3 * q + 2];
+            kind[i] = d2[i].y >> 24;
+            const uint32_t hdr = kind[i] == RXG_TXD_TCP ? 54u + 4u * ((d2[i].y >> 16) & 0xFFu) : 42u;
+            const uint32_t seg = (fl[i] == 0 || kind[i] == RXG_TXD_ARP) ? 0u : fl[i] - hdr;
+            uint32_t dd = 0; // the segment's first byte in the payload
+            if (kind[i] == RXG_TXD_TCP && mss) {
+                dd = j * mss;
+                d1[i].z += dd;
+                if ((uint64_t)dd + seg < d2[i].w) d2[i].y &= ~(0x09u << 8); // not the last: FIN, PSH
+            }
+            const uint32_t r = dd & 15u, hv = hdr - r;
+            f[i].fb = pkts + ((uint64_t)off[e] << 6);
+            f[i].pb = pay + ((uint64_t)d2[i].z << 4) + (dd & ~15u);
+            f[i].plen = seg ? (int32_t)(r + seg) : 0;
+            f[i].lo = (int32_t)r;
+            f[i].hc = (int32_t)((hv + 15u) >> 4);
+            f[i].k = ((16u - (hv & 15u)) - 2u) >> 2;
+            f[i].nb = (int32_t)((fl[i] + 63u) & ~63u);
+        }
+#pragma unroll
+        for (int i = 0; i < FPG; ++i)
+#pragma unroll
+            for (int q = 0; q < P; ++q) {
+                const int32_t a = ((s0 + q * STEP) >> 4) - f[i].hc + 1;
+                own[i][q] = txe_src<NB != 0, true>(f[i], a);
+                if constexpr (!NB) prv[i][q] = txe_src<false, true>(f[i], a - 1);
+            }
+#pragma unroll
+        for (int i = 0; i < FPG; ++i)
+            txe_frame_run<G, P, NB, true>(f[i], d0[i], d1[i], d2[i], kind[i], fl[i], own[i], prv[i],
+                                          gl, lane, (flags & RXG_TXE_NO_CKSUM) != 0);
+    }
+}
+
+template <int G, int P, int FPG, int NB>
+hipError_t launch_txe_tso(const uint4 *txd, const uint8_t *pay, uint8_t *pkts, const uint32_t *off,
+                          const uint16_t *len, const uint32_t *map, const uint32_t *first,
+                          const unsigned long long *need, uint32_t out_cap, uint32_t mss,
+                          uint32_t flags, uint32_t bpc_cap, hipStream_t s) {
+    constexpr uint32_t TILE = (256 / G) * FPG;
+    int cu = 0, occ = 0;
+    hipError_t e = rx_occupancy(reinterpret_cast<const void *>(tx_encode_tso_kernel<G, P, FPG, NB>),
+                                256, 0, &cu, &occ);
+    if (e != hipSuccess) return e;
+    // the entry count is on the device: the grid is sized for out_cap, blocks
+    // past the entries laid out leave at once
+    const uint64_t tiles = ((uint64_t)out_cap + TILE - 1) / TILE;
+    uint64_t bpc = (uint64_t)occ;
+    if (bpc_cap && bpc > bpc_cap) bpc = bpc_cap;
+    uint64_t blocks = (uint64_t)cu * bpc;
+    if (blocks > tiles || bpc_cap == TXE_FULL_GRID) blocks = tiles;
+    if (blocks > 0x7FFFFFFFull) blocks = 0x7FFFFFFFull; // (the tile loop strides)
+    if (blocks == 0) return hipSuccess;
+    hipLaunchKernelGGL((tx_encode_tso_kernel<G, P, FPG, NB>), dim3((uint32_t)blocks), dim3(256), 0, s,
+                       txd, pay, pkts, off, len, map, first, need, (unsigned long long)out_cap, mss,
+                       flags);
+    return hipGetLastError();
+}
+
+typedef hipError_t (*txe_tso_launch_fn)(const uint4 *, const uint8_t *, uint8_t *, const uint32_t *,
+                                        const uint16_t *, const uint32_t *, const uint32_t *,
+                                        const unsigned long long *, uint32_t, uint32_t, uint32_t,
+                                        uint32_t, hipStream_t);
+// the shapes of k_txe, index for index (rxg_tune_txe and len_hint choose both)
+static const txe_tso_launch_fn k_txe_tso[] = {
+    launch_txe_tso<4, 1, 4, 1>,  launch_txe_tso<4, 2, 2, 1>,  launch_txe_tso<8, 12, 1, 1>,
+    launch_txe_tso<16, 8, 1, 1>, launch_txe_tso<4, 1, 4, 0>,  launch_txe_tso<4, 2, 2, 0>,
+    launch_txe_tso<8, 12, 1, 0>, launch_txe_tso<16, 8, 1, 0>, launch_txe_tso<4, 1, 1, 1>,
+    launch_txe_tso<8, 1, 1, 1>,  launch_txe_tso<8, 4, 2, 1>,  launch_txe_tso<16, 6, 1, 1>,
+    launch_txe_tso<32, 4, 1, 1>, launch_txe_tso<32, 4, 1, 0>, launch_txe_tso<8, 1, 1, 0>,
+};
+static_assert(sizeof(k_txe_tso) / sizeof(k_txe_tso[0]) == sizeof(k_txe) / sizeof(k_txe[0]),
+              "one TSO kernel per k_txe entry");
+
+// the variant a len_hint chooses: the fastest of each class (k_txe's comment);
+// K2's class boundaries
+inline uint32_t txe_default_variant(uint32_t len_hint) {
+    if (len_hint == 0) len_hint = 1518;
+    return len_hint <= 64 ? 8 : (len_hint <= 128 ? 1 : (len_hint <= 600 ? 9 : (len_hint <= 1536 ? 11 : 12)));
+}
+
 } // namespace
+
+uint32_t txe_num_variants();
+
+size_t txe_tso_ws_bytes(uint32_t n, uint32_t out_cap) {
+    const uint64_t nchunks = ((uint64_t)n + TXE_CHUNK - 1) / TXE_CHUNK;
+    return 2 * (nchunks + 1) * 8 + TXE_PARTS * sizeof(txe_tso_part) + (uint64_t)n * 4 +
+           (uint64_t)out_cap * 4;
+}
+
+// the TSO layout pass, then the encoder over the entries; variant / bpc_cap as
+// tx_encode_launch
+hipError_t tx_encode_tso_launch(const void *txd_, uint32_t n, const uint8_t *pay, uint32_t mss,
+                                uint8_t *pkts, uint64_t cap, uint32_t slot, uint32_t *off,
+                                uint16_t *len, uint32_t out_cap, uint32_t *first, uint32_t *nseg,
+                                uint32_t len_hint, uint32_t flags, uint32_t *totals, void *ws,
+                                uint32_t variant, uint32_t bpc_cap, hipStream_t s) {
+    const uint4 *txd = reinterpret_cast<const uint4 *>(txd_);
+    const uint32_t nchunks = (uint32_t)(((uint64_t)n + TXE_CHUNK - 1) / TXE_CHUNK);
+    unsigned long long *sums_e = reinterpret_cast<unsigned long long *>(ws);
+    unsigned long long *sums_u = sums_e + nchunks + 1;
+    txe_tso_part *part = reinterpret_cast<txe_tso_part *>(sums_u + nchunks + 1);
+    uint32_t *posu = reinterpret_cast<uint32_t *>(part + TXE_PARTS);
+    uint32_t *map = posu + n;
+    const uint32_t nparts = nchunks < TXE_PARTS ? nchunks : TXE_PARTS;
+    hipError_t e = hipSuccess;
+    const uint64_t lim = 64ull << 32; // offsets are 32 bits of 64-B units
+    if (cap > lim) cap = lim;
+    hipLaunchKernelGGL(txe_tso_sums_kernel, dim3(nchunks), dim3(256), 0, s, txd, n, mss, slot, sums_e,
+                       sums_u);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(txe_tso_scan_kernel, dim3(2), dim3(1024), 0, s, sums_e, (uint64_t)nchunks);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(txe_tso_layout_kernel, dim3(nparts), dim3(256), 0, s, txd, n, mss, slot, sums_e,
+                       sums_u, (unsigned long long)cap, (unsigned long long)out_cap, first, nseg, posu,
+                       nchunks, part);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (out_cap) { // (sized for out_cap: the entry count is on the device)
+        const uint64_t eb = ((uint64_t)out_cap + 255) / 256;
+        hipLaunchKernelGGL(txe_tso_entries_kernel, dim3((uint32_t)(eb < 16384 ? eb : 16384)), dim3(256),
+                           0, s, txd, n, mss, slot, first, nseg, posu, sums_e + nchunks,
+                           (unsigned long long)out_cap, off, len, map);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(txe_tso_totals_kernel, dim3(1), dim3(256), 0, s, part, nparts, n,
+                       sums_e + nchunks, totals);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    uint32_t v = txe_default_variant(len_hint);
+    if (variant < txe_num_variants()) v = variant;
+    return k_txe_tso[v](txd, pay, pkts, off, len, map, first, sums_e + nchunks, out_cap, mss, flags,
+                        bpc_cap ? bpc_cap : k_txe[v].bpc, s);
+}
 
 uint32_t txe_num_variants() { return (uint32_t)(sizeof(k_txe) / sizeof(k_txe[0])); }
 

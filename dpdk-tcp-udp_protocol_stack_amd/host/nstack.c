@@ -864,6 +864,8 @@ static void restate_tcb(struct tcp_stream *s, int lookup_moves) {
 /* the GPU TX encoder's state (defined with nstack_tx_burst) */
 static int g_tx_encode;
 static atomic_ullong g_txe_frames;
+static uint32_t g_tx_mss;
+static atomic_ullong g_tso_frags;
 static void tx_stage_free(void);
 
 /* ---- lifecycle ---------------------------------------------------------- */
@@ -940,6 +942,8 @@ void nstack_fini(void) {
     g_inplace = 0; /* (options last one stack) */
     g_tx_encode = 0;
     atomic_store_explicit(&g_txe_frames, 0, memory_order_relaxed);
+    g_tx_mss = 0;
+    atomic_store_explicit(&g_tso_frags, 0, memory_order_relaxed);
     tx_stage_free();
     g_mb_release = NULL;
     g_mb_arg = NULL;
@@ -2912,6 +2916,20 @@ static rxg_txd *s_txd;
 static uint32_t s_txd_cap;
 static uint8_t *s_txpay;
 static uint64_t s_txpay_cap, s_txpay_len;
+/* TCP segmentation (nstack_set_tx_mss): tcp_out's walk sends a fragment longer
+ * than the MSS as several frames; 0 = off */
+static uint32_t g_tx_mss;
+static atomic_ullong g_tso_frags; /* stat 14 */
+static uint32_t *s_txseg;         /* rxg_tx_encode_tso's first / nseg */
+static uint32_t s_txseg_cap;
+
+int nstack_set_tx_mss(uint32_t mss) {
+    if (mss & 3u) return RXG_EINVAL;
+    pthread_mutex_lock(&g_lock);
+    g_tx_mss = mss;
+    pthread_mutex_unlock(&g_lock);
+    return 0;
+}
 
 int nstack_set_tx_encode(int on) {
     pthread_mutex_lock(&g_lock);
@@ -2922,10 +2940,10 @@ int nstack_set_tx_encode(int on) {
 
 static void tx_stage_free(void) {
     if (s_txpay && g_ctx) (void)rxg_unregister_host(g_ctx, s_txpay);
-    free(s_txpay), free(s_txd);
-    s_txpay = NULL, s_txd = NULL;
+    free(s_txpay), free(s_txd), free(s_txseg);
+    s_txpay = NULL, s_txd = NULL, s_txseg = NULL;
     s_txpay_cap = s_txpay_len = 0;
-    s_txd_cap = 0;
+    s_txd_cap = s_txseg_cap = 0;
 }
 
 /* room for `bytes` more staged payload bytes (to their 16-B end); 0 = no memory */
@@ -2945,14 +2963,14 @@ static int tx_stage_room(uint64_t bytes) {
     return 1;
 }
 
-/* descriptor k of the burst: its payload staged (the caller has made room),
- * the position advanced as tx_place does; kind RXG_TXD_ARP: ng_send_arp's
- * request for dip (enc_arp) */
+/* descriptor *nd of the burst: its payload staged (the caller has made room),
+ * the position advanced by its frames' `bytes` as tx_place does; kind
+ * RXG_TXD_ARP: ng_send_arp's request for dip (enc_arp) */
 static void tx_describe(uint32_t kind, const uint8_t *src_mac, const uint8_t *dst_mac, uint32_t sip,
                         uint32_t dip, const struct tcp_fragment *f, uint16_t sport, uint16_t dport,
-                        const uint8_t *data, uint32_t length, uint32_t fl, uint64_t *pos,
-                        uint32_t *n) {
-    rxg_txd *d = &s_txd[*n];
+                        const uint8_t *data, uint32_t length, uint64_t bytes, uint64_t *pos,
+                        uint32_t *nd) {
+    rxg_txd *d = &s_txd[*nd];
     memset(d, 0, sizeof(*d));
     memcpy(d->dst_mac, dst_mac, 6);
     memcpy(d->src_mac, src_mac, 6);
@@ -2972,8 +2990,8 @@ static void tx_describe(uint32_t kind, const uint8_t *src_mac, const uint8_t *ds
         else memset(s_txpay + s_txpay_len, 0, length);
         s_txpay_len += ((uint64_t)length + 15u) & ~15ull;
     }
-    *pos += align64(fl);
-    ++*n;
+    *pos += bytes;
+    ++*nd;
 }
 
 /* frame k of the burst: zero fill to the 64-B slot end, descriptor */
@@ -2992,9 +3010,10 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
     if (!pkts || !off || !len) return max_frames ? RXG_EINVAL : 0;
     reclaim();
     proto_lock();
-    uint32_t n = 0;
+    uint32_t n = 0, nd = 0; /* frames; the encoder's descriptors */
     uint64_t pos = 0;
     int full = 0;
+    const uint32_t mss = g_tx_mss;
     /* the GPU encoder: descriptors instead of frames (same walks, same rules) */
     int enc = g_tx_encode && cksum && max_frames;
     if (enc) {
@@ -3006,6 +3025,14 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
                 return RXG_ENOMEM;
             }
             s_txd = t, s_txd_cap = max_frames;
+        }
+        if (mss && s_txseg_cap < max_frames) {
+            uint32_t *t = realloc(s_txseg, (size_t)max_frames * 2 * sizeof(*t));
+            if (!t) {
+                pthread_mutex_unlock(&g_lock);
+                return RXG_ENOMEM;
+            }
+            s_txseg = t, s_txseg_cap = max_frames;
         }
     }
     /* udp_out, udp.c:123-164: at most one datagram per socket, list order */
@@ -3036,7 +3063,7 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
         if (!dmac) { /* an ARP request first, the datagram queued again (udp.c:139-146) */
             if (enc)
                 tx_describe(RXG_TXD_ARP, g_local_mac, k_default_arp_mac, o->sip, o->dip, NULL, 0, 0,
-                            NULL, 0, fl, &pos, &n);
+                            NULL, 0, align64(fl), &pos, &nd);
             else
                 enc_arp(fp, k_default_arp_mac, o->sip, o->dip);
             if (ring_enqueue(h->sndbuf, o)) {
@@ -3049,13 +3076,14 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
             pthread_mutex_unlock(&h->mutex);
             if (enc)
                 tx_describe(RXG_TXD_UDP, h->localmac, dmac, o->sip, o->dip, NULL, o->sport,
-                            o->dport, o->data, o->length, fl, &pos, &n);
+                            o->dport, o->data, o->length, align64(fl), &pos, &nd);
             else
                 enc_udp(fp, h->localmac, dmac, o);
             free(o->data);
             free(o);
         }
-        if (!enc) tx_place(fp, fl, &pos, off, len, &n);
+        if (enc) n++;
+        else tx_place(fp, fl, &pos, off, len, &n);
     }
     /* tcp_out, tcp.c:492-555: at most one fragment per tcb, list order */
     for (struct tcp_stream *s = g_tcb_set; s && n < max_frames && !full; s = s->next) {
@@ -3066,7 +3094,10 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
             continue;
         }
         const uint8_t *dmac = arp_lookup(s->sip); /* the remote side (tcp.c:521) */
-        const uint64_t fl64 = dmac ? 54u + (uint64_t)f->optlen * 4u + f->length : 42u;
+        /* longer than the MSS: s frames, each measured on its own */
+        const int tso = dmac && mss && f->length > mss;
+        const uint64_t fl64 =
+            dmac ? 54u + (uint64_t)f->optlen * 4u + (tso ? mss : f->length) : 42u;
         if (fl64 > 65535u) {
             tq_pop(s->sndbuf, &s->sq);
             pthread_mutex_unlock(&s->mutex);
@@ -3074,6 +3105,54 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
             continue;
         }
         const uint32_t fl = (uint32_t)fl64;
+        if (tso) {
+            /* the r whole segments that fit max_frames and cap_bytes go out now; r < s:
+             * FIN / PSH stay with the rest, which remains the head of the send queue */
+            const uint32_t hdr = fl - mss;
+            const uint32_t s_all = (uint32_t)(((uint64_t)f->length + mss - 1) / mss);
+            uint32_t r = 0;
+            uint64_t bytes = 0;
+            while (r < s_all && n + r < max_frames) {
+                const uint32_t sl = r + 1 == s_all ? f->length - r * mss : mss;
+                if (pos + bytes + align64(hdr + sl) > cap_bytes) break;
+                bytes += align64(hdr + sl);
+                r++;
+            }
+            const uint32_t take = r == s_all ? f->length : r * mss;
+            if (r == 0 || (enc && !tx_stage_room(take))) {
+                pthread_mutex_unlock(&s->mutex);
+                full = 1;
+                break;
+            }
+            struct tcp_fragment g = *f;
+            if (r < s_all) g.tcp_flags &= (uint8_t)~0x09u;
+            if (enc) { /* one descriptor: the encoder cuts it the same way */
+                tx_describe(RXG_TXD_TCP, s->localmac, dmac, s->dip, s->sip, &g, f->sport, f->dport,
+                            f->data, take, bytes, &pos, &nd);
+                n += r;
+            } else {
+                for (uint32_t j = 0; j < r; j++) {
+                    g.seqnum = f->seqnum + j * mss;
+                    g.data = f->data ? f->data + (size_t)j * mss : NULL;
+                    g.length = j + 1 == s_all ? f->length - j * mss : mss;
+                    g.tcp_flags = j + 1 == s_all ? f->tcp_flags : f->tcp_flags & (uint8_t)~0x09u;
+                    uint8_t *sp = pkts + pos;
+                    tx_place(sp, enc_tcp(sp, s->localmac, dmac, s->dip, s->sip, &g), &pos, off, len,
+                             &n);
+                }
+            }
+            if (r > 1) atomic_fetch_add_explicit(&g_tso_frags, 1, memory_order_relaxed);
+            if (r == s_all) {
+                tq_pop(s->sndbuf, &s->sq);
+            } else {
+                f->seqnum += take;
+                f->length -= take;
+                if (f->data) memmove(f->data, f->data + take, f->length);
+                full = 1;
+            }
+            pthread_mutex_unlock(&s->mutex);
+            continue;
+        }
         if (pos + align64(fl) > cap_bytes || (enc && !tx_stage_room(dmac ? f->length : 0))) {
             pthread_mutex_unlock(&s->mutex);
             full = 1;
@@ -3083,7 +3162,7 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
         if (!dmac) { /* tcp.c:522-535: an ARP request, the fragment dequeued and queued again */
             if (enc)
                 tx_describe(RXG_TXD_ARP, g_local_mac, k_default_arp_mac, s->dip, s->sip, NULL, 0, 0,
-                            NULL, 0, fl, &pos, &n);
+                            NULL, 0, align64(fl), &pos, &nd);
             else
                 enc_arp(fp, k_default_arp_mac, s->dip, s->sip);
             struct tcp_fragment *d = tq_detach(s->sndbuf, &s->sq);
@@ -3094,13 +3173,14 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
         } else {
             if (enc) /* local -> remote (tcp.c:542) */
                 tx_describe(RXG_TXD_TCP, s->localmac, dmac, s->dip, s->sip, f, f->sport, f->dport,
-                            f->data, f->length, fl, &pos, &n);
+                            f->data, f->length, align64(fl), &pos, &nd);
             else
                 enc_tcp(fp, s->localmac, dmac, s->dip, s->sip, f);
             tq_pop(s->sndbuf, &s->sq);
         }
         pthread_mutex_unlock(&s->mutex);
-        if (!enc) tx_place(fp, fl, &pos, off, len, &n);
+        if (enc) n++;
+        else tx_place(fp, fl, &pos, off, len, &n);
     }
     rxg_ctx *ctx = g_ctx;
     pthread_mutex_unlock(&g_lock);
@@ -3110,8 +3190,12 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
         int rc;
         if (enc) { /* K5 on the GPU: the frames, off and len of the walks' descriptors */
             uint64_t used = 0;
-            rc = rxg_tx_encode(ctx, s_txd, n, s_txpay, s_txpay_len, pkts, cap_bytes, off, len, 0,
-                               &used);
+            if (mss) /* n entries from nd descriptors */
+                rc = rxg_tx_encode_tso(ctx, s_txd, nd, s_txpay, s_txpay_len, mss, pkts, cap_bytes, off,
+                                       len, n, s_txseg, s_txseg + max_frames, 0, &used);
+            else
+                rc = rxg_tx_encode(ctx, s_txd, n, s_txpay, s_txpay_len, pkts, cap_bytes, off, len, 0,
+                                   &used);
             if (rc == RXG_OK && used != pos) rc = RXG_ERANGE;
             if (rc == RXG_OK) atomic_fetch_add_explicit(&g_txe_frames, n, memory_order_relaxed);
         } else {
@@ -3123,7 +3207,8 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
 }
 
 uint64_t nstack_stat(int which) {
-    if (which < 0 || which > 13) return 0;
+    if (which < 0 || which > 14) return 0;
+    if (which == 14) return (uint64_t)atomic_load_explicit(&g_tso_frags, memory_order_relaxed);
     if (which == 13) return (uint64_t)atomic_load_explicit(&g_txe_frames, memory_order_relaxed);
     if (which == 12) return (uint64_t)atomic_load_explicit(&g_deliveries, memory_order_acquire);
     if (which == 7) return (uint64_t)atomic_load_explicit(&g_pl_batches, memory_order_relaxed);

@@ -232,6 +232,13 @@ _tx_encode = _sig("rxg_tx_encode", _i32, _vp, _vp, _u32, _vp, _u64, _vp, _u64, _
                   C.POINTER(_u64))
 _tx_encode_host = _sig("rxg_tx_encode_host", _i32, _vp, _u32, _vp, _u64, _vp, _u64, _u32, _vp, _vp,
                        _u32, C.POINTER(_u64), _vp)
+_tx_encode_tso_dev = _sig("rxg_tx_encode_tso_dev", _i32, _vp, _vp, _u32, _vp, _u32, _vp, _u64, _u32,
+                          _vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp)
+_tx_encode_tso = _sig("rxg_tx_encode_tso", _i32, _vp, _vp, _u32, _vp, _u64, _u32, _vp, _u64, _vp, _vp,
+                      _u32, _vp, _vp, _u32, C.POINTER(_u64))
+_tx_encode_tso_host = _sig("rxg_tx_encode_tso_host", _i32, _vp, _u32, _vp, _u64, _u32, _vp, _u64, _u32,
+                           _vp, _vp, _u32, _vp, _vp, _u32, C.POINTER(_u64), _vp)
+_tx_tso_count = _sig("rxg_tx_tso_count", _i32, _vp, _u32, _u32, C.POINTER(_u64), C.POINTER(_u64))
 _tune_txe = _sig("rxg_tune_txe", _i32, _vp, _u32, _u32)
 _rss_split = _sig("rxg_rss_split", _i32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp)
 _rss_split_dev = _sig("rxg_rss_split_dev", _i32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp,
@@ -260,7 +267,8 @@ EXPORTED = ["rxg_open", "rxg_close", "rxg_strerror", "rxg_last_hip_error", "rxg_
             "rxg_rss_hash", "rxg_gen_flows", "rxg_gen_host", "rxg_gen_dev", "rxg_submit", "rxg_wait",
             "rxg_pcap_open", "rxg_pcap_close", "rxg_pcap_rewind", "rxg_pcap_read_burst",
             "rxg_pcap_write", "rxg_tx_cksum_dev", "rxg_tx_cksum", "rxg_tx_encode_dev",
-            "rxg_tx_encode", "rxg_tx_encode_host", "rxg_tune_txe", "rxg_rss_split",
+            "rxg_tx_encode", "rxg_tx_encode_host", "rxg_tx_encode_tso_dev", "rxg_tx_encode_tso",
+            "rxg_tx_encode_tso_host", "rxg_tx_tso_count", "rxg_tune_txe", "rxg_rss_split",
             "rxg_rss_split_dev", "rxg_gather_dev", "rxg_group_id", "rxg_group_open",
             "rxg_group_close", "rxg_group_size", "rxg_counts_allreduce", "rxg_ctx_counts_allreduce"]
 
@@ -595,6 +603,37 @@ class Context:
                               p(d_off), p(d_len), len_hint, flags, p(d_totals), stream),
                "rxg_tx_encode_dev")
 
+    def tx_encode_tso(self, txd: np.ndarray, payload: np.ndarray, mss: int, cap_bytes: int,
+                      out_cap: int, flags: int = 0):
+        """frames of a host descriptor burst with TCP payloads cut at mss, packed
+        (PCIe round trip): (pkts[:span], off, len, first, nseg, rc); off / len
+        hold out_cap entries (zero where nothing was written), rc is 0 or
+        RXG_ERANGE (something was skipped)"""
+        txd = np.ascontiguousarray(txd, TXD_DTYPE)
+        payload = np.ascontiguousarray(payload, np.uint8)
+        n = len(txd)
+        pk = np.zeros(max(cap_bytes, 1), np.uint8)
+        off, ln = np.zeros(max(out_cap, 1), np.uint32), np.zeros(max(out_cap, 1), np.uint16)
+        first, nseg = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        span = _u64()
+        rc = _tx_encode_tso(self._h, _ptr(txd), n, _ptr(payload), len(payload), mss, _ptr(pk),
+                            cap_bytes, _ptr(off), _ptr(ln), out_cap, _ptr(first), _ptr(nseg), flags,
+                            C.byref(span))
+        if rc not in (0, -34):
+            _check(rc, "rxg_tx_encode_tso")
+        return pk[:span.value], off[:out_cap], ln[:out_cap], first[:n], nseg[:n], rc
+
+    def tx_encode_tso_dev(self, d_txd, n: int, d_payload, mss: int, d_pkts, cap_bytes: int,
+                          slot_bytes: int, d_off, d_len, out_cap: int, d_first, d_nseg,
+                          len_hint: int, flags: int, d_totals, stream=None):
+        """frames of a device descriptor burst with TCP payloads cut at mss (torch
+        tensors or raw ints), asynchronous; d_totals has 8 words"""
+        def p(x):
+            return x if (x is None or isinstance(x, int)) else x.data_ptr()
+        _check(_tx_encode_tso_dev(self._h, p(d_txd), n, p(d_payload), mss, p(d_pkts), cap_bytes,
+                                  slot_bytes, p(d_off), p(d_len), out_cap, p(d_first), p(d_nseg),
+                                  len_hint, flags, p(d_totals), stream), "rxg_tx_encode_tso_dev")
+
     def process_mbufs(self, mbufs) -> np.ndarray:
         arr = (C.POINTER(Mbuf) * len(mbufs))(*[C.pointer(m) for m in mbufs])
         out = np.zeros(len(mbufs), VERDICT_DTYPE)
@@ -700,6 +739,39 @@ def tx_encode_host(txd: np.ndarray, payload: np.ndarray, cap_bytes: int, slot_by
     if rc not in (0, -34):
         _check(rc, "rxg_tx_encode_host")
     return pk, off, ln, span.value, tot, rc
+
+
+def tx_tso_count(txd: np.ndarray, mss: int):
+    """rxg_tx_tso_count: (entries, packed_bytes) a burst needs at this mss"""
+    txd = np.ascontiguousarray(txd, TXD_DTYPE)
+    e, b = _u64(), _u64()
+    _check(_tx_tso_count(txd.ctypes.data if len(txd) else None, len(txd), mss, C.byref(e),
+                         C.byref(b)), "rxg_tx_tso_count")
+    return e.value, b.value
+
+
+def tx_encode_tso_host(txd: np.ndarray, payload: np.ndarray, mss: int, cap_bytes: int, out_cap: int,
+                       slot_bytes: int = 0, flags: int = 0, fill: int = 0, fill_entries: int = 0):
+    """rxg_tx_encode_tso_host, the TX encoder with TCP segmentation on the CPU:
+    (pkts, off, len, first, nseg, span, totals, rc); pkts is the whole
+    cap_bytes buffer prefilled with `fill`, off / len hold out_cap entries
+    prefilled with `fill_entries` (all bits), so a caller can see what was left
+    untouched; rc is 0 or RXG_ERANGE, anything else raises"""
+    txd = np.ascontiguousarray(txd, TXD_DTYPE)
+    payload = np.ascontiguousarray(payload, np.uint8)
+    n = len(txd)
+    pk = np.full(cap_bytes, fill, np.uint8)
+    off = np.full(max(out_cap, 1), fill_entries & 0xFFFFFFFF, np.uint32)
+    ln = np.full(max(out_cap, 1), fill_entries & 0xFFFF, np.uint16)
+    first, nseg = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+    span, tot = _u64(), np.zeros(8, np.uint32)
+    rc = _tx_encode_tso_host(txd.ctypes.data, n, payload.ctypes.data if len(payload) else None,
+                             len(payload), mss, pk.ctypes.data, cap_bytes, slot_bytes, off.ctypes.data,
+                             ln.ctypes.data, out_cap, first.ctypes.data, nseg.ctypes.data, flags,
+                             C.byref(span), tot.ctypes.data)
+    if rc not in (0, -34):
+        _check(rc, "rxg_tx_encode_tso_host")
+    return pk, off[:out_cap], ln[:out_cap], first[:n], nseg[:n], span.value, tot, rc
 
 
 def rss_hash(sip: int, dip: int, sport: int, dport: int) -> int:
@@ -860,7 +932,8 @@ class NStack:
                    ("nstack_set_local", _i32, [_u32, _vp]),
                    ("nstack_arp_insert", _i32, [_u32, _vp]),
                    ("nstack_tx_burst", _i32, [_vp, _u64, _vp, _vp, _u32, _i32, _vp]),
-                   ("nstack_set_tx_encode", _i32, [_i32])]
+                   ("nstack_set_tx_encode", _i32, [_i32]),
+                   ("nstack_set_tx_mss", _i32, [_u32])]
             for name, res, args in sig:
                 f = getattr(lib, name)
                 f.restype, f.argtypes = res, args
@@ -1157,6 +1230,12 @@ class NStack:
         """nstack_set_tx_encode: tx_burst(cksum=True) builds its frames on the
         GPU (K5) from descriptors instead of framing them on the host"""
         return self.lib.nstack_set_tx_encode(1 if on else 0)
+
+    def set_tx_mss(self, mss: int):
+        """nstack_set_tx_mss: tcp_out sends a fragment longer than mss (a multiple
+        of 4; 0 = off) as MSS-sized frames"""
+        _check(self.lib.nstack_set_tx_mss(mss), "nstack_set_tx_mss")
+        return 0
 
     def tx_burst(self, max_frames: int = 256, cap_bytes: int = 1 << 20, cksum: bool = False):
         """one udp_out + tcp_out pass: the frames (bytes) it produced"""

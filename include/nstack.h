@@ -191,6 +191,23 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
  * Default off; with cksum == 0 the host frames as before.  nstack_stat(13)
  * counts the frames the encoder produced.  Returns 0. */
 int nstack_set_tx_encode(int on);
+/* TCP segmentation for tcp_out's walk.  mss == 0 (the default): off, a
+ * fragment is one frame of any length, as nsend queued it (common.c:418-460).
+ * mss != 0 (a multiple of 4, else RXG_EINVAL; rxg_tx_encode_tso's rule): a
+ * fragment longer than mss is sent as s = ceil(length / mss) frames with
+ * consecutive sequence numbers, FIN / PSH only on the last.  It needs s of
+ * max_frames and the segments' 64-B-rounded bytes of cap_bytes.  If only
+ * r < s whole segments fit and r > 0, those r go out now with FIN / PSH
+ * cleared, the fragment stays at the head of the send queue with seqnum,
+ * data and length advanced by r * mss, and the pass is full; r == 0: it
+ * stays queued and the pass ends, as at a full buffer.  Both framing paths
+ * honour it: the host emits the segments itself, the encoder path
+ * (nstack_set_tx_encode) passes one descriptor per fragment to
+ * rxg_tx_encode_tso; frames, off, len, *span, return value (frames) and
+ * queue state are the same.  The 65535-B drop rule then applies to a
+ * segment's frame.  nstack_stat(14) counts the times a fragment went out as
+ * more than one frame in a pass.  Returns 0. */
+int nstack_set_tx_mss(uint32_t mss);
 
 /* The application side of a benchmark, in one call: every UDP socket read
  * with nrecvfrom until empty, every tcb's receive queue read (nrecv) and its
@@ -270,7 +287,8 @@ int nstack_set_halves(uint32_t min_half);
  * polling application that reads a value it has not seen finds that burst's
  * items in its next nstack_drain_all (bumped with release order after the
  * deliveries, read with acquire); 13 = frames produced by the TX encoder
- * (nstack_set_tx_encode).  Counter 1 also counts TX items dropped (a
+ * (nstack_set_tx_encode); 14 = fragments sent as more than one frame in a
+ * pass (nstack_set_tx_mss).  Counter 1 also counts TX items dropped (a
  * send ring full, or a datagram too long for a frame). */
 uint64_t nstack_stat(int which);
 

@@ -545,6 +545,71 @@ int rxg_tx_encode_host(const rxg_txd *txd, uint32_t n, const uint8_t *payload,
                        uint32_t slot_bytes, uint32_t *off, uint16_t *len, uint32_t flags,
                        uint64_t *span, uint32_t totals[4]);
 
+/* TX encode with TCP segmentation (TSO): a RXG_TXD_TCP descriptor whose
+ * payload is longer than `mss` becomes s = ceil(pay_len / mss) frames from
+ * the one descriptor, the payload read once.  Segment j (0 <= j < s) is the
+ * frame ng_encode_tcp_apppkt (tcp.c:420-466) writes for the descriptor with
+ * payload bytes [j*mss, min((j+1)*mss, pay_len)), seq + j*mss (mod 2^32), and
+ * FIN (0x01) / PSH (0x08) cleared unless j == s-1; everything else (MACs,
+ * addresses, ports, ack, window, urp, hdrlen_off, zero option words) is the
+ * descriptor's, both checksums are filled per segment and each frame is
+ * zero-filled to its 64-B boundary.  UDP and ARP descriptors are never cut
+ * (no IP fragmentation); pay_len 0 gives one segment.  mss == 0: nothing is
+ * cut; mss must be a multiple of 4 (RXG_EINVAL), so that every segment's
+ * payload starts 4-B aligned in the payload buffer and lands 2 mod 4 in its
+ * frame, the one phase the kernel's funnel knows.
+ *
+ * Output is per entry (frame), not per descriptor:
+ *  1. s_k, the segment count of descriptor k, follows from its kind and
+ *     lengths alone: 0 for an unknown kind, or when a segment's frame
+ *     (hdr + min(mss, pay_len); the whole frame for UDP / ARP / mss == 0)
+ *     exceeds 65535 bytes or slot_bytes.  Descriptor k owns the entries
+ *     [first_k, first_k + max(1, s_k)), first_k = sum over i < k of
+ *     max(1, s_i) in 64 bits; d_first[k] = first_k, saturated at 2^32-1.
+ *  2. A descriptor is written whole or not at all: iff s_k > 0,
+ *     first_k + s_k <= out_cap (the capacity of d_off / d_len in entries)
+ *     and its frames fit cap_bytes.
+ *  3. Packed (slot_bytes == 0): its segments follow each other at 64-B
+ *     alignment, and the first descriptor that does not fit cap_bytes ends
+ *     the burst.  Slots: entry e sits at e * slot_bytes.
+ *  4. A written descriptor gets d_nseg[k] = s_k and off (64-B units) / len
+ *     for its entries; a skipped one d_nseg[k] = 0 and off = len = 0 for each
+ *     of its entries below out_cap.
+ *  5. Bytes outside [slot start, 64-B-rounded frame end) of written frames
+ *     are never touched; nothing is written at or past entry out_cap.
+ * d_totals has 8 words: {frames written, span bytes low, high, descriptors
+ * skipped, entries needed low, high, 0, 0}.  With mss == 0 (or every TCP
+ * pay_len <= mss) and out_cap >= n, pkts / off / len / totals[0..3] are those
+ * of rxg_tx_encode_dev, first[k] = k and nseg[k] = (len[k] != 0).  The kernel
+ * variant is chosen as rxg_tx_encode_dev chooses it (len_hint, rxg_tune_txe).
+ * The workspace also holds an entry -> descriptor map of out_cap words and a
+ * position word per descriptor. */
+int rxg_tx_encode_tso_dev(rxg_ctx *ctx, const rxg_txd *d_txd, uint32_t n, const uint8_t *d_payload,
+                          uint32_t mss, uint8_t *d_pkts, uint64_t cap_bytes, uint32_t slot_bytes,
+                          uint32_t *d_off, uint16_t *d_len, uint32_t out_cap, uint32_t *d_first,
+                          uint32_t *d_nseg, uint32_t len_hint, uint32_t flags, uint32_t *d_totals,
+                          void *stream);
+/* Host form (packed), as rxg_tx_encode: off / len hold out_cap entries, first
+ * / nseg n descriptors.  RXG_ERANGE if any descriptor was skipped; RXG_EINVAL
+ * for a bad mss or a payload that ends past payload_bytes. */
+int rxg_tx_encode_tso(rxg_ctx *ctx, const rxg_txd *txd, uint32_t n, const uint8_t *payload,
+                      uint64_t payload_bytes, uint32_t mss, uint8_t *pkts, uint64_t cap_bytes,
+                      uint32_t *off, uint16_t *len, uint32_t out_cap, uint32_t *first,
+                      uint32_t *nseg, uint32_t flags, uint64_t *span);
+/* The same on the CPU (csrc/tx_encode_host.cpp), as rxg_tx_encode_host;
+ * totals (nullable) has 8 words. */
+int rxg_tx_encode_tso_host(const rxg_txd *txd, uint32_t n, const uint8_t *payload,
+                           uint64_t payload_bytes, uint32_t mss, uint8_t *pkts, uint64_t cap_bytes,
+                           uint32_t slot_bytes, uint32_t *off, uint16_t *len, uint32_t out_cap,
+                           uint32_t *first, uint32_t *nseg, uint32_t flags, uint64_t *span,
+                           uint32_t totals[8]);
+/* Sizes the outputs of a burst (host, no device): *entries = the sum of
+ * max(1, s_k) (what out_cap must reach for nothing to be skipped for it),
+ * *packed_bytes = the packed frames' bytes (slot_bytes == 0) if nothing is
+ * skipped for capacity.  Either may be NULL.  RXG_EINVAL for a bad mss. */
+int rxg_tx_tso_count(const rxg_txd *txd, uint32_t n, uint32_t mss, uint64_t *entries,
+                     uint64_t *packed_bytes);
+
 /* Tuning hook for the TX encode kernel: force entry `variant` of its variant
  * table (csrc/tx_encode.hip k_txe; RXG_TX_AUTO = chosen from len_hint) and cap
  * its resident blocks per CU (0 = the variant's default). */
