@@ -726,7 +726,10 @@ uint32_t rxg_rss_hash(uint32_t sip, uint32_t dip, uint16_t sport, uint16_t dport
  * first[s] = start of shard s in perm, first[n_shards] = n (n_shards + 1
  * entries).  Host form: host buffers, synchronous.  Device form: device
  * buffers, asynchronous on `stream` (workspace grown on demand, between
- * bursts). */
+ * bursts).  Readable extent, rxg_rss_split_dev and rxg_gather_dev: each frame
+ * must be readable to its 16-B end (pkts + (off << off_unit_log2) rounded up
+ * from len to a multiple of 16), and a zero-length frame's offset must be
+ * readable for 16 B (the kernels load whole 16-B chunks and mask them). */
 int rxg_rss_split(const uint8_t *pkts, const uint32_t *off, const uint16_t *len, uint32_t n,
                   uint32_t off_unit_log2, uint32_t n_shards, uint32_t *first, uint32_t *perm);
 int rxg_rss_split_dev(rxg_ctx *ctx, const uint8_t *d_pkts, const uint32_t *d_off,
