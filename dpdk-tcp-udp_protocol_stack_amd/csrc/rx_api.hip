@@ -68,6 +68,11 @@ hipError_t rx_segsort_launch(const uint8_t *pkts, const uint32_t *off, const uin
                              uint32_t n, uint32_t unit_log2, const uint4 *verd, uint32_t nt,
                              rxg_segment *seg, uint8_t *payload, uint64_t cap, uint32_t *totals,
                              void *ws, hipStream_t s);
+size_t rx_gro_ws_bytes(uint32_t n);
+hipError_t rx_gro_launch(const uint8_t *pkts, const uint32_t *off, const uint16_t *len, uint32_t n,
+                         uint32_t unit_log2, const uint4 *verd, uint32_t nt, uint32_t W,
+                         rxg_segment *seg, rxg_tcp_run *run, uint8_t *payload, uint64_t cap,
+                         uint32_t *totals, void *ws, hipStream_t s);
 size_t rx_compact_ws_bytes(uint32_t n, uint32_t nflows);
 hipError_t rx_compact_launch(const uint8_t *pkts, const uint32_t *off, const uint16_t *len,
                              uint32_t n, uint32_t unit_log2, const uint4 *verd, uint32_t nflows,
@@ -196,6 +201,7 @@ struct rxg_ctx {
     uint32_t tune_tables = 0; // rxg_tune_tables flags
     uint32_t tune_ingest = RXG_INGEST_AUTO; // rxg_tune_ingest
     uint32_t deliver_flags = 0;             // rxg_tune_deliver (RXG_DLV_*)
+    uint32_t gro_window = RXG_GRO_DEFAULT_WINDOW; // rxg_tune_gro (RXG_DLV_TCP_GRO)
     rx_ft_dev ft{};
     uint32_t tune_g = 0, tune_p = 0, tune_fpg = 0, tune_pipe = ~0u; // rxg_tune override
     uint32_t tune_bpc = 0; // rxg_tune_grid: resident blocks per CU cap (0 = occupancy)
@@ -274,6 +280,7 @@ struct rxg_ctx {
     // results and their pinned host copies, sized by max_pkts / max_bytes
     rxg_segment *d_ss_seg = nullptr;
     uint8_t *d_ss_payload = nullptr;
+    rxg_tcp_run *d_ss_run = nullptr; // (RXG_DLV_TCP_GRO: first use)
     // pinned payload buffers a caller may keep past the next burst
     // (rxg_payload_hold / _release: the receive fragments of a burst point
     // into them until the application has read them); refs counts the holds,
@@ -287,7 +294,9 @@ struct rxg_ctx {
     // device buffers are shared: every step runs on `stream`, in order) and its
     // phase events; a set's results stay valid until the set is reused
     struct delivery_set {
-        bool on = false, udp = false, tcp = false;
+        bool on = false, udp = false, tcp = false, gro = false;
+        uint32_t nrun = 0;             // (rxg_delivery_runs)
+        rxg_tcp_run *h_ss_run = nullptr;
         uint64_t ticket = 0;
         double t0 = 0, t1 = 0;
         int pl = -1; // the pooled payload buffer the library holds for this set
@@ -758,12 +767,13 @@ void rxg_close(rxg_ctx *c) {
     (void)hipFree(c->d_cp_ws);
     (void)hipFree(c->d_ss_seg);
     (void)hipFree(c->d_ss_payload);
+    (void)hipFree(c->d_ss_run);
     (void)hipFree(c->d_ss_totals);
     (void)hipFree(c->d_ss_ws);
     for (rxg_ctx::delivery_set &ds : c->dls) {
         for (void *h : {(void *)ds.h_cp_dg, (void *)ds.h_cp_first, (void *)ds.h_cp_totals,
                         (void *)ds.h_cp_payload, (void *)ds.h_ss_seg, (void *)ds.h_ss_payload,
-                        (void *)ds.h_ss_totals})
+                        (void *)ds.h_ss_totals, (void *)ds.h_ss_run})
             if (h) (void)hipHostFree(h);
         for (hipEvent_t e : ds.tev)
             if (e) (void)hipEventDestroy(e);
@@ -1158,8 +1168,16 @@ int rxg_tune_tables(rxg_ctx *c, uint32_t flags) {
 }
 
 int rxg_tune_deliver(rxg_ctx *c, uint32_t flags) {
-    if (!c || (flags & ~RXG_DLV_TCP_IN_PLACE)) return RXG_EINVAL;
+    if (!c || (flags & ~(RXG_DLV_TCP_IN_PLACE | RXG_DLV_TCP_GRO))) return RXG_EINVAL;
+    // (payloads that stay in their frames cannot be made contiguous)
+    if ((flags & RXG_DLV_TCP_IN_PLACE) && (flags & RXG_DLV_TCP_GRO)) return RXG_EINVAL;
     c->deliver_flags = flags;
+    return RXG_OK;
+}
+
+int rxg_tune_gro(rxg_ctx *c, uint32_t W) {
+    if (!c || W > RXG_GRO_MAX_WINDOW) return RXG_EINVAL;
+    c->gro_window = W ? W : RXG_GRO_DEFAULT_WINDOW;
     return RXG_OK;
 }
 
@@ -1741,6 +1759,21 @@ static int segsort_impl(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off
     return RXG_OK;
 }
 
+// K4 with receive coalescing (rx_segsort.hip); the workspace is K4's, grown
+static int gro_impl(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off, const uint16_t *d_len,
+                    uint32_t n, uint32_t off_unit_log2, const uint4 *d_v, uint32_t W,
+                    rxg_segment *d_seg, rxg_tcp_run *d_run, uint8_t *d_payload, uint64_t cap,
+                    uint32_t *d_totals, hipStream_t s) {
+    const size_t ws = rx_gro_ws_bytes(n);
+    if (ws > c->d_ss_ws_cap) {
+        int rc = ensure_dev_async(&c->d_ss_ws, &c->d_ss_ws_cap, ws, s);
+        if (rc) return rc;
+    }
+    HIPCHK(rx_gro_launch(d_pkts, d_off, d_len, n, off_unit_log2, d_v, c->fs.tcp.id_space(), W, d_seg,
+                         d_run, d_payload, cap, d_totals, c->d_ss_ws, s));
+    return RXG_OK;
+}
+
 int rxg_payload_hold(rxg_ctx *c, int32_t ref) {
     if (!c || ref < 0 || ref >= RXG_PAYLOAD_BUFS) return RXG_EINVAL;
     c->pl[ref].refs.fetch_add(1, std::memory_order_acq_rel);
@@ -1765,6 +1798,32 @@ int rxg_tcp_compact_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off
     DEVGUARD(c);
     return segsort_impl(c, d_pkts, d_off, d_len, n, off_unit_log2, reinterpret_cast<const uint4 *>(d_v),
                         d_seg, d_payload, payload_cap, d_totals, (hipStream_t)stream);
+}
+
+int rxg_tcp_coalesce_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off,
+                         const uint16_t *d_len, uint32_t n, uint32_t off_unit_log2,
+                         const rxg_verdict *d_v, uint32_t W, rxg_segment *d_seg, rxg_tcp_run *d_run,
+                         uint8_t *d_payload, uint64_t payload_cap, uint32_t *d_totals, void *stream) {
+    if (!c) return RXG_EINVAL;
+    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
+    if (!d_totals || !d_payload || (n && (!d_pkts || !d_off || !d_len || !d_v || !d_seg || !d_run)))
+        return RXG_EINVAL;
+    if (W < 1u || W > RXG_GRO_MAX_WINDOW) return RXG_EINVAL;
+    if (off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
+    DEVGUARD(c);
+    return gro_impl(c, d_pkts, d_off, d_len, n, off_unit_log2, reinterpret_cast<const uint4 *>(d_v), W,
+                    d_seg, d_run, d_payload, payload_cap, d_totals, (hipStream_t)stream);
+}
+
+int rxg_delivery_runs(rxg_ctx *c, const rxg_delivery *d, const rxg_tcp_run **run, uint32_t *nrun) {
+    if (!c || !d || !run || !nrun) return RXG_EINVAL;
+    *run = nullptr;
+    *nrun = 0;
+    if (d->set < 1 || d->set > RXG_DELIVER_DEPTH) return RXG_EINVAL;
+    const rxg_ctx::delivery_set &ds = c->dls[d->set - 1];
+    if (ds.on) return RXG_EINVAL; // (not waited for yet)
+    if (ds.gro && ds.nrun) *run = ds.h_ss_run, *nrun = ds.nrun;
+    return RXG_OK;
 }
 
 static double now_ms() {
@@ -1811,6 +1870,12 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
             HIPCHK(hipHostMalloc((void **)&ds.h_ss_seg, (size_t)c->max_pkts * sizeof(rxg_segment), 0));
         HIPCHK(hipHostMalloc((void **)&ds.h_ss_totals, 4 * sizeof(uint32_t), 0));
     }
+    const bool gro = (c->deliver_flags & RXG_DLV_TCP_GRO) != 0;
+    if (gro) {
+        if (!c->d_ss_run) HIPCHK(hipMalloc(&c->d_ss_run, (size_t)c->max_pkts * sizeof(rxg_tcp_run)));
+        if (!ds.h_ss_run)
+            HIPCHK(hipHostMalloc((void **)&ds.h_ss_run, (size_t)c->max_pkts * sizeof(rxg_tcp_run), 0));
+    }
     for (hipEvent_t &e : ds.tev)
         if (!e) HIPCHK(hipEventCreate(&e));
     // the TCP payloads of this burst: a free pooled buffer (a hold the caller
@@ -1845,7 +1910,8 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
         d->udp_payload = ds.h_cp_payload;
         memset(ds.h_cp_first, 0, (nf + 1) * sizeof(uint32_t));
     }
-    ds.on = ds.udp = ds.tcp = false;
+    ds.on = ds.udp = ds.tcp = ds.gro = false;
+    ds.nrun = 0;
     ds.ticket = 0;
     ds.t0 = t0;
     c->dl_next = (si + 1) % RXG_DELIVER_DEPTH;
@@ -1873,11 +1939,17 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
                                    c->stream)))
                 return rc;
         tcp = c->fs.tcp.id_space() > 0;
-        if (tcp)
+        if (tcp && gro) {
+            if ((rc = gro_impl(c, sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, sl.d_out, c->gro_window,
+                               c->d_ss_seg, c->d_ss_run, c->d_ss_payload, c->max_bytes,
+                               c->d_ss_totals, c->stream)))
+                return rc;
+        } else if (tcp) {
             if ((rc = segsort_impl(c, sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, sl.d_out, c->d_ss_seg,
                                    inplace ? nullptr : c->d_ss_payload, c->max_bytes,
                                    c->d_ss_totals, c->stream)))
                 return rc;
+        }
         HIPCHK(hipEventRecord(ds.tev[3], c->stream)); // after K3 / K4
         // every result in one round trip: the counts with upper-bound copies of
         // the records (n of each) and payloads (the staged span bounds the sum of
@@ -1895,8 +1967,11 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
                                   c->stream));
         }
         if (tcp) {
-            HIPCHK(hipMemcpyAsync(ds.h_ss_totals, c->d_ss_totals, 3 * sizeof(uint32_t),
+            HIPCHK(hipMemcpyAsync(ds.h_ss_totals, c->d_ss_totals, (gro ? 4 : 3) * sizeof(uint32_t),
                                   hipMemcpyDeviceToHost, c->stream));
+            if (gro) // (the runs cross with the records: at most n of them)
+                HIPCHK(hipMemcpyAsync(ds.h_ss_run, c->d_ss_run, (size_t)n * sizeof(rxg_tcp_run),
+                                      hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipMemcpyAsync(ds.h_ss_seg, c->d_ss_seg, (size_t)n * sizeof(rxg_segment),
                                   hipMemcpyDeviceToHost, c->stream));
             if (!inplace)
@@ -1915,6 +1990,7 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
     ds.on = true;
     ds.udp = udp;
     ds.tcp = tcp;
+    ds.gro = tcp && gro;
     ds.ticket = t;
     ds.t1 = t1;
     return RXG_OK;
@@ -1939,6 +2015,7 @@ int rxg_deliver_wait(rxg_ctx *c, rxg_delivery *d, float ms[8]) {
         return RXG_ERANGE; // (not reached: staging bounds the payloads)
     if (udp) d->ndgram = ds.h_cp_totals[0], d->udp_bytes = ds.h_cp_totals[1];
     if (tcp) d->nseg = ds.h_ss_totals[0], d->tcp_bytes = ds.h_ss_totals[1];
+    if (ds.gro) ds.nrun = ds.h_ss_totals[3];
     if (ms) {
         ms[0] = (float)(ds.t1 - ds.t0);
         for (int k = 0; k < 4; ++k) HIPCHK(hipEventElapsedTime(&ms[k + 1], ds.tev[k], ds.tev[k + 1]));

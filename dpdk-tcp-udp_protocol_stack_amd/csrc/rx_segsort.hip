@@ -330,3 +330,404 @@ hipError_t rx_segsort_launch(const uint8_t *pkts, const uint32_t *off, const uin
                        s, pkts, off, len, unit_log2, tsum, seg, payload, cap, totals);
     return hipGetLastError();
 }
+
+// ---- Receive coalescing (GRO): K4 with the in-sequence trains of a
+// connection laid down as contiguous byte ranges (the rule: include/rxgpu.h,
+// "TCP receive coalescing"; restated on the host in rx_gro_host.cpp).  After
+// the same sort, three rounds of block scan + one-block scan of the block sums:
+//   1. records, link flags, G[j] = the sum of ncopy before j and the last
+//      chain head at or before j (a max scan); inside a chain ncopy == plen,
+//      so b[j] = G[j] - G[head];
+//   2. run heads from b and the window, counted into run ids;
+//   3. per run: first record, count, bytes; the 16-B padded sizes scanned
+//      into the runs' offsets;
+// then a wave per segment copies its payload to run offset + G[j] - G[first].
+// No chain is walked: one connection may own the whole burst.
+namespace {
+
+#define GRO_HEADBIT 0x80000000u
+
+// ss_wave_scan with max for +: the lanes shifted in read 0, the identity of
+// max on unsigned values as well
+__device__ __forceinline__ uint32_t gro_wave_max(uint32_t x) {
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x111, 0xF, 0xF, true));
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x112, 0xF, 0xF, true));
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x114, 0xF, 0xF, true));
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x118, 0xF, 0xF, true));
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x142, 0xA, 0xF, false));
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x143, 0xC, 0xF, false));
+    return x;
+}
+
+// inclusive scan (sum or max) over the block's SS_THREADS values, every
+// thread calling; ws: SS_THREADS / 64 words of LDS of this scan's own;
+// total = the block's sum / max
+template <bool MAX>
+__device__ __forceinline__ uint32_t gro_block_scan(uint32_t x, uint32_t *ws, uint32_t &total) {
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    const uint32_t inc = MAX ? gro_wave_max(x) : ss_wave_scan(x);
+    if (lane == 63u) ws[w] = inc;
+    __syncthreads();
+    uint32_t pre = 0u, all = 0u;
+#pragma unroll
+    for (uint32_t q = 0; q < SS_THREADS / 64u; ++q) {
+        const uint32_t v = ws[q];
+        if (q < w) pre = MAX ? max(pre, v) : pre + v;
+        all = MAX ? max(all, v) : all + v;
+    }
+    total = all;
+    return MAX ? max(inc, pre) : inc + pre;
+}
+
+// exclusive scan in place of a block array of 64-bit values, one block (a
+// thread per contiguous chunk): m = the blocks of *cnt items; block 0 sums
+// a_sum (*total, nullable, = the sum), block 1 (when launched) takes the
+// running max of a_max
+__global__ __launch_bounds__(1024) void gro_scan_kernel(uint64_t *__restrict__ a_sum,
+                                                        uint64_t *__restrict__ a_max,
+                                                        const uint32_t *__restrict__ cnt,
+                                                        uint64_t *__restrict__ total) {
+    __shared__ uint64_t ws[16];
+    const bool mx = blockIdx.x == 1u;
+    uint64_t *a = mx ? a_max : a_sum;
+    const uint32_t m = (uint32_t)(((uint64_t)cnt[0] + SS_THREADS - 1u) / SS_THREADS);
+    const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
+    const uint32_t per = (m + 1023u) / 1024u;
+    const uint32_t b0 = min(m, t * per), b1 = min(m, b0 + per);
+    auto op = [mx](uint64_t x, uint64_t y) -> uint64_t { return mx ? (x > y ? x : y) : x + y; };
+    uint64_t s = 0u;
+    for (uint32_t k = b0; k < b1; ++k) s = op(s, a[k]);
+    uint64_t inc = s;
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const uint64_t y = __shfl_up((unsigned long long)inc, d);
+        if (lane >= d) inc = op(inc, y);
+    }
+    // exclusive over the lanes: the inclusive value of the lane below
+    uint64_t run = __shfl_up((unsigned long long)inc, 1u);
+    if (lane == 0u) run = 0u;
+    if (lane == 63u) ws[w] = inc;
+    __syncthreads();
+    for (uint32_t q = 0; q < w; ++q) run = op(run, ws[q]);
+    if (t == 1023u && total && !mx) *total = op(run, s);
+    for (uint32_t k = b0; k < b1; ++k) {
+        const uint64_t x = a[k];
+        a[k] = run;
+        run = op(run, x);
+    }
+}
+
+// what a record's successor must match to link to it
+struct gro_key {
+    uint32_t flow, sip, ports, ack, seq, next_seq, merge;
+};
+
+// the record of sorted segment j, field for field ss_record_kernel's (offset
+// left 0), and its link key
+__device__ __forceinline__ rxg_segment gro_decode(const uint8_t *__restrict__ pkts,
+                                                  const uint32_t *__restrict__ off,
+                                                  const uint16_t *__restrict__ len,
+                                                  uint32_t unit_log2, const uint32_t *__restrict__ keys,
+                                                  const uint32_t *__restrict__ vals, uint32_t j,
+                                                  gro_key &k) {
+    rxg_segment s;
+    const uint32_t i = vals[j];
+    const uint8_t *f = pkts + ((uint64_t)off[i] << unit_log2);
+    const uint32_t cap = len[i];
+    auto b = [&](uint32_t q) -> uint32_t { return q < cap ? (uint32_t)f[q] : 0u; };
+    const uint32_t tl = (b(16) << 8) | b(17);
+    s.frame = i;
+    s.flow = keys[j];
+    s.seq = (b(38) << 24) | (b(39) << 16) | (b(40) << 8) | b(41);
+    s.ack = (b(42) << 24) | (b(43) << 16) | (b(44) << 8) | b(45);
+    s.hl = (uint8_t)(b(46) >> 4);
+    s.flags = (uint8_t)b(47);
+    s.plen = (int32_t)tl - 20 - 4 * (int32_t)s.hl;
+    s.sport = (uint16_t)(b(34) | (b(35) << 8));
+    s.dport = (uint16_t)(b(36) | (b(37) << 8));
+    const uint32_t from = 34u + 4u * s.hl;
+    const uint32_t avail = cap > from ? cap - from : 0u;
+    const uint32_t keep = ((s.flags & 0x08u) && s.plen > 0) ? min((uint32_t)s.plen, avail) : 0u;
+    s.ncopy = (uint16_t)keep;
+    s.offset = 0u;
+    k.flow = s.flow;
+    k.sip = b(26) | (b(27) << 8) | (b(28) << 16) | (b(29) << 24);
+    k.ports = (uint32_t)s.sport | ((uint32_t)s.dport << 16);
+    k.ack = s.ack;
+    k.seq = s.seq;
+    k.next_seq = s.seq + (uint32_t)s.plen;
+    k.merge = s.flags == 0x18u && s.hl == 5u && s.plen > 0 && (int32_t)keep == s.plen;
+    return s;
+}
+
+// round 1: the records; gl[j] = the block's sum of ncopy before j; hd[j] =
+// 1 + the last chain head at or before j inside the block (0: none yet);
+// bG / bH[block] = the block's sum / last head
+__global__ __launch_bounds__(SS_THREADS) void gro_record_kernel(
+    const uint8_t *__restrict__ pkts, const uint32_t *__restrict__ off,
+    const uint16_t *__restrict__ len, uint32_t unit_log2, const uint32_t *__restrict__ keys,
+    const uint32_t *__restrict__ vals, const uint32_t *__restrict__ totals,
+    rxg_segment *__restrict__ seg, uint32_t *__restrict__ gl, uint32_t *__restrict__ hd,
+    uint64_t *__restrict__ bG, uint64_t *__restrict__ bH) {
+    __shared__ gro_key key[SS_THREADS + 1u];
+    __shared__ uint32_t ws_g[SS_THREADS / 64u], ws_h[SS_THREADS / 64u];
+    const uint32_t nseg = totals[0];
+    const uint32_t t = threadIdx.x;
+    const uint32_t j0 = blockIdx.x * SS_THREADS, j = j0 + t;
+    if (j0 >= nseg) return; // (uniform)
+    gro_key k = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    uint32_t c = 0u;
+    if (j < nseg) {
+        const rxg_segment s = gro_decode(pkts, off, len, unit_log2, keys, vals, j, k);
+        seg[j] = s;
+        c = s.ncopy;
+    }
+    key[t + 1u] = k;
+    if (t == 0u) { // the block's predecessor record
+        gro_key p = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
+        if (j0) (void)gro_decode(pkts, off, len, unit_log2, keys, vals, j0 - 1u, p);
+        key[0] = p;
+    }
+    __syncthreads();
+    const gro_key p = key[t];
+    const bool link = j && p.merge && k.merge && p.flow == k.flow && p.sip == k.sip &&
+                      p.ports == k.ports && p.ack == k.ack && k.seq == p.next_seq;
+    uint32_t gsum, hmax;
+    const uint32_t ginc = gro_block_scan<false>(c, ws_g, gsum);
+    const uint32_t hinc = gro_block_scan<true>((j < nseg && !link) ? j + 1u : 0u, ws_h, hmax);
+    if (j < nseg) {
+        gl[j] = ginc - c;
+        hd[j] = hinc;
+    }
+    if (t == 0u) {
+        bG[blockIdx.x] = gsum;
+        bH[blockIdx.x] = hmax;
+    }
+}
+
+// round 2 (bG, bH scanned): record j starts a run iff it heads its chain or
+// the window index of b changes from j-1 to j; rl[j] = the block's count of
+// run heads up to and including j, GRO_HEADBIT set on a head; bR[block] = the
+// block's count
+__global__ __launch_bounds__(SS_THREADS) void gro_runhead_kernel(
+    const rxg_segment *__restrict__ seg, const uint32_t *__restrict__ totals, uint32_t W,
+    const uint32_t *__restrict__ gl, const uint32_t *__restrict__ hd,
+    const uint64_t *__restrict__ bG, const uint64_t *__restrict__ bH, uint32_t *__restrict__ rl,
+    uint64_t *__restrict__ bR) {
+    __shared__ uint32_t ws[SS_THREADS / 64u];
+    const uint32_t nseg = totals[0];
+    const uint32_t t = threadIdx.x;
+    const uint32_t j0 = blockIdx.x * SS_THREADS, j = j0 + t;
+    if (j0 >= nseg) return; // (uniform)
+    uint32_t rh = 0u;
+    if (j < nseg) {
+        // the chain's head: inside the block, else the last one of the blocks
+        // before (record 0 heads a chain, so there is one)
+        const uint32_t h1 = hd[j] ? hd[j] : (uint32_t)bH[blockIdx.x];
+        rh = 1u;
+        if (h1 != j + 1u) { // j links to j-1
+            const uint32_t h = h1 - 1u;
+            const uint64_t b = (gl[j] + bG[blockIdx.x]) - (gl[h] + bG[h / SS_THREADS]);
+            const uint64_t pb = b - (uint32_t)seg[j - 1u].plen;
+            rh = b / W != pb / W;
+        }
+    }
+    uint32_t total;
+    const uint32_t inc = gro_block_scan<false>(rh, ws, total);
+    if (j < nseg) rl[j] = inc | (rh ? GRO_HEADBIT : 0u);
+    if (t == 0u) bR[blockIdx.x] = total;
+}
+
+// (bR scanned, tot[1] = the runs) rl[j] becomes j's run id; a run's head
+// leaves its index in rfirst[run]
+__global__ __launch_bounds__(SS_THREADS) void gro_runid_kernel(uint32_t *__restrict__ totals,
+                                                              const uint64_t *__restrict__ tot,
+                                                              uint32_t *__restrict__ rl,
+                                                              const uint64_t *__restrict__ bR,
+                                                              uint32_t *__restrict__ rfirst) {
+    const uint32_t nseg = totals[0];
+    const uint32_t j = blockIdx.x * SS_THREADS + threadIdx.x;
+    if (j == 0u) totals[3] = (uint32_t)tot[1];
+    if (j >= nseg) return;
+    const uint32_t v = rl[j];
+    const uint32_t id = (v & ~GRO_HEADBIT) + (uint32_t)bR[blockIdx.x] - 1u;
+    rl[j] = id;
+    if (v & GRO_HEADBIT) rfirst[id] = j;
+}
+
+// round 3: the run records (offset in gro_copy_kernel); ol[r] = the block's
+// sum of the 16-B padded run sizes before r, bO[block] the block's sum
+__global__ __launch_bounds__(SS_THREADS) void gro_run_kernel(
+    const uint32_t *__restrict__ totals, const uint64_t *__restrict__ tot,
+    const uint32_t *__restrict__ gl, const uint64_t *__restrict__ bG,
+    const uint32_t *__restrict__ rfirst, rxg_tcp_run *__restrict__ run, uint32_t *__restrict__ ol,
+    uint64_t *__restrict__ bO) {
+    __shared__ uint32_t ws[SS_THREADS / 64u];
+    const uint32_t nseg = totals[0], nrun = (uint32_t)tot[1];
+    const uint32_t t = threadIdx.x;
+    const uint32_t r0 = blockIdx.x * SS_THREADS, r = r0 + t;
+    if (r0 >= nrun) return; // (uniform)
+    uint32_t padded = 0u;
+    if (r < nrun) {
+        const uint32_t first = rfirst[r], next = r + 1u < nrun ? rfirst[r + 1u] : nseg;
+        const uint64_t g0 = gl[first] + bG[first / SS_THREADS];
+        const uint64_t g1 = next < nseg ? gl[next] + bG[next / SS_THREADS] : tot[0];
+        rxg_tcp_run x;
+        x.first = first;
+        x.nseg = next - first;
+        x.bytes = (uint32_t)(g1 - g0);
+        x.offset = 0u;
+        run[r] = x;
+        padded = (x.bytes + 15u) & ~15u;
+    }
+    uint32_t total;
+    const uint32_t inc = gro_block_scan<false>(padded, ws, total);
+    if (r < nrun) ol[r] = inc - padded;
+    if (t == 0u) bO[blockIdx.x] = total;
+}
+
+// a wave per segment (bO scanned, tot[2] = the payload bytes used): its
+// offset = its run's offset + the run's ncopy before it, at any byte phase;
+// then its payload, bytes [34 + 4*hl, + ncopy) of the frame: the bytes up to
+// the first 16-B boundary of the destination and those after the last one as
+// byte stores, the chunks between as 16-B stores (dword loads realigned with
+// v_alignbyte, the source at any phase now); the run's last segment zeroes the
+// bytes to the 16-B padded end.  Every byte has one writer and no lane reads
+// the destination.
+__global__ __launch_bounds__(SS_THREADS) void gro_copy_kernel(
+    const uint8_t *__restrict__ pkts, const uint32_t *__restrict__ off,
+    const uint16_t *__restrict__ len, uint32_t unit_log2, const uint64_t *__restrict__ tot,
+    const uint32_t *__restrict__ gl, const uint64_t *__restrict__ bG,
+    const uint32_t *__restrict__ rl, const uint32_t *__restrict__ rfirst,
+    const uint32_t *__restrict__ ol, const uint64_t *__restrict__ bO, rxg_segment *__restrict__ seg,
+    rxg_tcp_run *__restrict__ run, uint8_t *__restrict__ payload, uint64_t cap,
+    uint32_t *__restrict__ totals) {
+    const uint32_t nseg = totals[0];
+    const uint32_t j = blockIdx.x * (SS_THREADS / 64u) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (blockIdx.x == 0u && threadIdx.x == 0u) totals[1] = (uint32_t)tot[2];
+    if (j >= nseg) return;
+    const rxg_segment s = seg[j];
+    const uint32_t r = rl[j], first = rfirst[r];
+    const uint64_t ro = ol[r] + bO[r / SS_THREADS];
+    const uint32_t rbytes = run[r].bytes;
+    const uint64_t o =
+        ro + ((gl[j] + bG[j / SS_THREADS]) - (gl[first] + bG[first / SS_THREADS]));
+    if (lane == 0u) {
+        seg[j].offset = (uint32_t)o;
+        if (j == first) run[r].offset = (uint32_t)ro;
+    }
+    if (ro + ((rbytes + 15u) & ~15u) > cap) { // the whole run stays unwritten
+        if (lane == 0u && j == first) atomicOr(&totals[2], 1u);
+        return;
+    }
+    const uint32_t ncopy = s.ncopy;
+    const bool last = j + 1u == nseg || rl[j + 1u] != r;
+    if (last && lane >= 32u && lane < 48u) { // the zero tail: [run end, padded end)
+        const uint64_t end = o + ncopy;
+        if (lane - 32u < ((16u - (uint32_t)(end & 15u)) & 15u)) payload[end + (lane - 32u)] = 0u;
+    }
+    if (!ncopy) return;
+    const uint8_t *f = pkts + ((uint64_t)off[s.frame] << unit_log2);
+    const uint32_t fcap = len[s.frame];
+    const uint32_t src = 34u + 4u * s.hl;
+    const uint32_t hlen = min(ncopy, (16u - (uint32_t)(o & 15u)) & 15u);
+    const uint32_t nb = (ncopy - hlen) >> 4, tb = hlen + 16u * nb, tlen = ncopy - tb;
+    if (lane < hlen) payload[o + lane] = src + lane < fcap ? f[src + lane] : (uint8_t)0u;
+    if (lane >= 16u && lane - 16u < tlen) {
+        const uint32_t q = tb + (lane - 16u);
+        payload[o + q] = src + q < fcap ? f[src + q] : (uint8_t)0u;
+    }
+    for (uint32_t c = lane; c < nb; c += 64u) {
+        const uint32_t a = src + hlen + 16u * c, a0 = a & ~3u, sh = a & 3u;
+        uint32_t wv[5];
+#pragma unroll
+        for (uint32_t q = 0; q < 5u; ++q) {
+            const uint32_t p = a0 + 4u * q;
+            wv[q] = p < fcap ? *reinterpret_cast<const uint32_t *>(f + p) : 0u;
+        }
+        uint32_t o4[4];
+#pragma unroll
+        for (uint32_t q = 0; q < 4u; ++q)
+            o4[q] = sh ? __builtin_amdgcn_alignbyte(wv[q + 1], wv[q], sh) : wv[q];
+        *reinterpret_cast<uint4 *>(payload + o + hlen + 16u * c) =
+            make_uint4(o4[0], o4[1], o4[2], o4[3]);
+    }
+}
+
+} // namespace
+
+// workspace: K4's, then five words per frame (gl, hd, rl, rfirst, ol), four
+// 64-bit block arrays (bG, bH, bR, bO) and the three 64-bit totals
+size_t rx_gro_ws_bytes(uint32_t n) {
+    const size_t nn = n ? n : 1;
+    return rx_segsort_ws_bytes(n) + 5 * ss_align(nn * 4) +
+           4 * ss_align((size_t)(ss_blocks(n) ? ss_blocks(n) : 1) * 8) + 256;
+}
+
+// d_totals: 4 (segments, payload bytes, overflow flag, runs)
+hipError_t rx_gro_launch(const uint8_t *pkts, const uint32_t *off, const uint16_t *len, uint32_t n,
+                         uint32_t unit_log2, const uint4 *verd, uint32_t nt, uint32_t W,
+                         rxg_segment *seg, rxg_tcp_run *run, uint8_t *payload, uint64_t cap,
+                         uint32_t *totals, void *ws, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(totals, 0, 4 * sizeof(uint32_t), s);
+    if (e != hipSuccess || n == 0 || nt == 0) return e;
+    const size_t nn = ss_align((size_t)n * 4);
+    uint8_t *w8 = static_cast<uint8_t *>(ws);
+    uint32_t *ka = reinterpret_cast<uint32_t *>(w8), *va = reinterpret_cast<uint32_t *>(w8 + nn);
+    uint32_t *kb = reinterpret_cast<uint32_t *>(w8 + 2 * nn), *vb = reinterpret_cast<uint32_t *>(w8 + 3 * nn);
+    const uint32_t ntiles = ss_tiles(n), nblk = ss_blocks(n);
+    uint32_t *hist = reinterpret_cast<uint32_t *>(w8 + 4 * nn);
+    uint8_t *g8 = w8 + rx_segsort_ws_bytes(n);
+    uint32_t *gl = reinterpret_cast<uint32_t *>(g8), *hd = reinterpret_cast<uint32_t *>(g8 + nn);
+    uint32_t *rl = reinterpret_cast<uint32_t *>(g8 + 2 * nn);
+    uint32_t *rfirst = reinterpret_cast<uint32_t *>(g8 + 3 * nn);
+    uint32_t *ol = reinterpret_cast<uint32_t *>(g8 + 4 * nn);
+    const size_t nb8 = ss_align((size_t)nblk * 8);
+    uint64_t *bG = reinterpret_cast<uint64_t *>(g8 + 5 * nn);
+    uint64_t *bH = reinterpret_cast<uint64_t *>(g8 + 5 * nn + nb8);
+    uint64_t *bR = reinterpret_cast<uint64_t *>(g8 + 5 * nn + 2 * nb8);
+    uint64_t *bO = reinterpret_cast<uint64_t *>(g8 + 5 * nn + 3 * nb8);
+    uint64_t *tot = reinterpret_cast<uint64_t *>(g8 + 5 * nn + 4 * nb8); // {sum of ncopy, runs, bytes used}
+    if ((e = hipMemsetAsync(tot, 0, 3 * sizeof(uint64_t), s)) != hipSuccess) return e;
+    // the sort, as in rx_segsort_launch
+    const uint32_t bits = 32u - (uint32_t)__builtin_clz(nt);
+    const uint32_t passes = (bits + 7u) / 8u;
+    const uint32_t *kin = nullptr, *vin = nullptr;
+    uint32_t *kout = ka, *vout = va;
+    for (uint32_t p = 0; p < passes; ++p) {
+        const uint32_t shift = 8u * p;
+        if (p == 0)
+            hipLaunchKernelGGL(ss_hist_kernel<true>, dim3(ntiles), dim3(SS_THREADS), 0, s, verd,
+                               nullptr, n, nt, shift, ntiles, hist, totals);
+        else
+            hipLaunchKernelGGL(ss_hist_kernel<false>, dim3(ntiles), dim3(SS_THREADS), 0, s, verd,
+                               kin, n, nt, shift, ntiles, hist, totals);
+        hipLaunchKernelGGL(ss_scan_kernel, dim3(1), dim3(1024), 0, s, hist, SS_DIGITS * ntiles,
+                           nullptr);
+        if (p == 0)
+            hipLaunchKernelGGL(ss_scatter_kernel<true>, dim3(ntiles), dim3(SS_THREADS), 0, s, verd,
+                               nullptr, nullptr, n, nt, shift, ntiles, hist, kout, vout);
+        else
+            hipLaunchKernelGGL(ss_scatter_kernel<false>, dim3(ntiles), dim3(SS_THREADS), 0, s, verd,
+                               kin, vin, n, nt, shift, ntiles, hist, kout, vout);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        kin = kout, vin = vout;
+        kout = (kout == ka) ? kb : ka;
+        vout = (vout == va) ? vb : va;
+    }
+    hipLaunchKernelGGL(gro_record_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, pkts, off, len,
+                       unit_log2, kin, vin, totals, seg, gl, hd, bG, bH);
+    hipLaunchKernelGGL(gro_scan_kernel, dim3(2), dim3(1024), 0, s, bG, bH, totals, tot);
+    hipLaunchKernelGGL(gro_runhead_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, seg, totals, W, gl,
+                       hd, bG, bH, rl, bR);
+    hipLaunchKernelGGL(gro_scan_kernel, dim3(1), dim3(1024), 0, s, bR, nullptr, totals, tot + 1);
+    hipLaunchKernelGGL(gro_runid_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, totals, tot, rl, bR,
+                       rfirst);
+    hipLaunchKernelGGL(gro_run_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, totals, tot, gl, bG,
+                       rfirst, run, ol, bO);
+    hipLaunchKernelGGL(gro_scan_kernel, dim3(1), dim3(1024), 0, s, bO, nullptr,
+                       reinterpret_cast<const uint32_t *>(tot + 1), tot + 2);
+    hipLaunchKernelGGL(gro_copy_kernel, dim3((uint32_t)(((uint64_t)n + 3) / 4)), dim3(SS_THREADS), 0,
+                       s, pkts, off, len, unit_log2, tot, gl, bG, rl, rfirst, ol, bO, seg, run,
+                       payload, cap, totals);
+    return hipGetLastError();
+}

@@ -327,6 +327,13 @@ static atomic_ullong g_deliveries;
  * the put that drops the count to 0 hands the mbuf to g_mb_release (the
  * mempool's free, rte_pktmbuf_free). */
 static int g_inplace;
+/* Receive coalescing (nstack_set_rx_gro): the window in bytes, 0 = off; a
+ * connection's in-sequence PSH|ACK trains arrive as runs (rxg_tcp_run) and
+ * each run of more than one segment makes one receive fragment and one ACK.
+ * g_gro_absorbed (stat 15): segments that went into a preceding segment's
+ * fragment. */
+static uint32_t g_gro;
+static uint64_t g_gro_absorbed;
 static void (*g_mb_release)(rxg_mbuf *m, void *arg);
 static void *g_mb_arg;
 static inline void mb_get(rxg_mbuf *m) { __atomic_fetch_add(&m->refcnt, 1, __ATOMIC_RELAXED); }
@@ -875,6 +882,10 @@ int nstack_init(int device, uint32_t max_burst, uint64_t max_bytes) {
     if (!g_ctx) {
         rc = rxg_open(&g_ctx, device, max_burst, max_bytes);
         if (rc == RXG_OK && g_inplace) rxg_tune_deliver(g_ctx, RXG_DLV_TCP_IN_PLACE);
+        if (rc == RXG_OK && g_gro) {
+            rxg_tune_deliver(g_ctx, RXG_DLV_TCP_GRO);
+            rxg_tune_gro(g_ctx, g_gro);
+        }
         /* a new context: its delivery sets start again at set 0 */
         for (uint32_t j = 0; j < RXG_DELIVER_DEPTH; j++) g_set_ref[j] = -1;
         g_next_set = 0;
@@ -940,6 +951,8 @@ void nstack_fini(void) {
     memset(g_local_mac, 0, sizeof(g_local_mac));
     reclaim(); /* (what the blocks' last puts let go of) */
     g_inplace = 0; /* (options last one stack) */
+    g_gro = 0;
+    g_gro_absorbed = 0;
     g_tx_encode = 0;
     atomic_store_explicit(&g_txe_frames, 0, memory_order_relaxed);
     g_tx_mss = 0;
@@ -1682,9 +1695,9 @@ static int deliver_burst(rxg_mbuf *const *m, uint32_t n, const rxg_verdict *v, i
     return delivered;
 }
 
-static void deliver_tcp_sorted(const rxg_segment *sg, uint32_t nseg, const uint8_t *payload,
-                               int32_t pl_ref, rxg_mbuf *const *m, uint8_t *handled,
-                               int *rc_out);
+static void deliver_tcp_sorted(const rxg_segment *sg, uint32_t nseg, const rxg_tcp_run *run,
+                               uint32_t nrun, const uint8_t *payload, int32_t pl_ref,
+                               rxg_mbuf *const *m, uint8_t *handled, int *rc_out);
 static uint32_t host_segments(rxg_mbuf *const *m, uint32_t n, const rxg_verdict *v,
                               rxg_segment *sg);
 static int deliver_udp_batches(rxg_mbuf *const *m, const rxg_dgram *dg, const uint32_t *first,
@@ -1776,7 +1789,25 @@ int nstack_deliver(rxg_mbuf *const *m, uint32_t n, const rxg_verdict *v, uint64_
             if (!grow((void **)&s_handled, &s_handled_cap, n, 1) && sg) {
                 memset(s_handled, 0, n);
                 const uint32_t k = host_segments(m, n, v, sg);
-                deliver_tcp_sorted(sg, k, NULL, -1, m, s_handled, rc_out);
+                /* coalescing: the runs by the rule's host restatement, the
+                 * source addresses read from the mbufs (out of memory: the
+                 * segments one by one) */
+                rxg_tcp_run *run = NULL;
+                uint32_t nrun = 0;
+                uint32_t *sip = g_gro && k ? malloc((size_t)k * sizeof(*sip)) : NULL;
+                if (sip) run = malloc((size_t)k * sizeof(*run));
+                if (run) {
+                    for (uint32_t j = 0; j < k; j++) {
+                        const rxg_mbuf *mb = m[sg[j].frame];
+                        const uint8_t *f = (const uint8_t *)mb->buf_addr + mb->data_off;
+                        sip[j] = 0;
+                        for (uint32_t q = 0; q < 4; q++)
+                            if (26u + q < mb->data_len) sip[j] |= (uint32_t)f[26u + q] << (8u * q);
+                    }
+                    if (rxg_tcp_runs_host(sg, sip, k, g_gro, run, &nrun) != RXG_OK) nrun = 0;
+                }
+                deliver_tcp_sorted(sg, k, nrun ? run : NULL, nrun, NULL, -1, m, s_handled, rc_out);
+                free(sip), free(run);
                 done = s_handled;
             }
             free(sg);
@@ -1869,8 +1900,17 @@ static int deliver_udp_batches(rxg_mbuf *const *m, const rxg_dgram *dg, const ui
  * payload was captured whole points straight into it (no copy: the batch
  * holds the buffer until it is freed); otherwise the payload is copied, zero
  * filled past the capture.  Returns 0, or 1 when the tcb's state needs the
- * frame-by-frame path (LISTEN, SYN_RCVD, LAST_ACK). */
+ * frame-by-frame path (LISTEN, SYN_RCVD, LAST_ACK).
+ * Receive coalescing (run non-NULL: the connection's nr runs, run[].first
+ * counted from sg - base): a run of more than one segment — in-sequence
+ * PSH|ACK segments with equal ack, payloads captured whole and byte-contiguous
+ * at the run's offset — makes one fragment of the run's bytes (pointing into
+ * the held buffer, else copied) and one ACK, whose acknum is rcv_nxt after the
+ * run: the ACK that closes the run in the segment-by-segment order.  A run of
+ * one takes the segment's path.  A full receive ring drops whole runs.
+ * Connections on the frame-by-frame path are never coalesced. */
 static int deliver_tcp_conn(struct tcp_stream *s, const rxg_segment *sg, uint32_t k,
+                            const rxg_tcp_run *run, uint32_t nr, uint32_t base,
                             const uint8_t *payload, int32_t pl_ref, rxg_mbuf *const *m,
                             uint8_t *handled, int *rc_out) {
     if (s->status == TCP_STATUS_LISTEN || s->status == TCP_STATUS_SYN_RCVD ||
@@ -1882,10 +1922,22 @@ static int deliver_tcp_conn(struct tcp_stream *s, const rxg_segment *sg, uint32_
     uint64_t pbytes = 0;
     int st = s->status;
     const int inpl = g_inplace; /* payloads captured whole stay in their frames */
+    uint32_t ri = 0; /* the run that holds segment j */
     for (uint32_t j = 0; j < k; j++) {
         handled[sg[j].frame] = 1;
         if (rc_out) rc_out[sg[j].frame] = RXG_RC_OK;
         if (st != TCP_STATUS_ESTABLISHED) continue;
+        if (run) {
+            while (ri + 1 < nr && run[ri + 1].first - base <= j) ri++;
+            if (run[ri].nseg > 1) { /* one fragment, one ACK for the run */
+                if (run[ri].first - base == j) {
+                    nfr++, nack++;
+                    if (pl_ref < 0) pbytes += run[ri].bytes; /* (copied) */
+                    g_gro_absorbed += run[ri].nseg - 1;
+                }
+                continue;
+            }
+        }
         if (sg[j].flags & TCP_PSH) {
             nfr++, nack++;
             if (sg[j].plen > 0 && sg[j].ncopy != (uint32_t)sg[j].plen) /* cut short: copied */
@@ -1980,8 +2032,49 @@ static int deliver_tcp_conn(struct tcp_stream *s, const rxg_segment *sg, uint32_
             }                                                                                \
             ai++;                                                                            \
         } while (0)
+    ri = 0;
     for (uint32_t j = 0; j < k && s->status == TCP_STATUS_ESTABLISHED; j++) {
         const rxg_segment *g = &sg[j];
+        if (run) {
+            while (ri + 1 < nr && run[ri + 1].first - base <= j) ri++;
+            if (run[ri].nseg > 1) { /* (j is the run's first segment) */
+                const rxg_tcp_run *r = &run[ri];
+                if (fi < rtake && rb) {
+                    struct tcp_fragment *fr = &rb->frag[fi];
+                    memset(fr, 0, sizeof(*fr));
+                    fr->dport = ntohs(g->dport);
+                    fr->sport = ntohs(g->sport);
+                    fr->length = r->bytes;
+                    if (pl_ref >= 0) {
+                        fr->data = (unsigned char *)payload + r->offset; /* (no copy) */
+                        rb->pl_ref = pl_ref;
+                    } else {
+                        fr->data = pp;
+                        if (payload) {
+                            memcpy(pp, payload + r->offset, r->bytes);
+                            pp += r->bytes;
+                        } else { /* (host verdicts: from the frames) */
+                            for (uint32_t q = 0; q < r->nseg; q++) {
+                                const rxg_mbuf *mb_ = m[g[q].frame];
+                                memcpy(pp, (const uint8_t *)mb_->buf_addr + mb_->data_off + 34u +
+                                               4u * g[q].hl, g[q].ncopy);
+                                pp += g[q].ncopy;
+                            }
+                        }
+                        g_copied_bytes += r->bytes;
+                    }
+                    g_stat[4]++;
+                } else {
+                    g_stat[1]++;
+                }
+                fi++;
+                s->rcv_nxt += r->bytes;
+                s->snd_nxt = g->ack;
+                PUT_ACK(g);
+                j += r->nseg - 1;
+                continue;
+            }
+        }
         if (g->flags & TCP_PSH) { /* tcp.c:226-262 */
             PUT_FRAG(g, g->plen);
             s->rcv_nxt += (uint32_t)g->plen;
@@ -2025,9 +2118,10 @@ static int deliver_tcp_conn(struct tcp_stream *s, const rxg_segment *sg, uint32_
 
 /* the sorted segments, connection by connection (g_lock held); frames of
  * connections that need the frame-by-frame path are left unmarked */
-static void deliver_tcp_sorted(const rxg_segment *sg, uint32_t nseg, const uint8_t *payload,
-                               int32_t pl_ref, rxg_mbuf *const *m, uint8_t *handled,
-                               int *rc_out) {
+static void deliver_tcp_sorted(const rxg_segment *sg, uint32_t nseg, const rxg_tcp_run *run,
+                               uint32_t nrun, const uint8_t *payload, int32_t pl_ref,
+                               rxg_mbuf *const *m, uint8_t *handled, int *rc_out) {
+    uint32_t r0 = 0; /* (coalescing) the first run of the connection: runs never span two */
     for (uint32_t a = 0, b; a < nseg; a = b) {
         b = a + 1;
         while (b < nseg && sg[b].flow == sg[a].flow) b++;
@@ -2038,7 +2132,13 @@ static void deliver_tcp_sorted(const rxg_segment *sg, uint32_t nseg, const uint8
         if (g_inplace)
             for (uint32_t j = b; j < b + 8 && j < nseg; j++) __builtin_prefetch(m[sg[j].frame], 1, 0);
         struct tcp_stream *s = sg[a].flow < s_tcb_cap ? s_tcb_cb[sg[a].flow] : NULL;
-        if (s) deliver_tcp_conn(s, sg + a, b - a, payload, pl_ref, m, handled, rc_out);
+        uint32_t r1 = r0;
+        if (run)
+            while (r1 < nrun && run[r1].first < b) r1++;
+        if (s)
+            deliver_tcp_conn(s, sg + a, b - a, run && r1 > r0 ? run + r0 : NULL, r1 - r0, a, payload,
+                             pl_ref, m, handled, rc_out);
+        r0 = r1;
     }
 }
 
@@ -2163,7 +2263,12 @@ static int deliver_part(rxg_mbuf *const *m, uint32_t k, const rxg_verdict *v, ui
     }
     const double t2 = mono_ms();
     memset(handled, 0, k);
-    if (d->nseg) deliver_tcp_sorted(d->seg, d->nseg, d->tcp_payload, d->tcp_payload_ref, m, handled, rco);
+    const rxg_tcp_run *run = NULL; /* (coalescing on at the submit: the burst's runs) */
+    uint32_t nrun = 0;
+    if (d->nseg && g_gro && rxg_delivery_runs(g_ctx, d, &run, &nrun) != RXG_OK) run = NULL, nrun = 0;
+    if (d->nseg)
+        deliver_tcp_sorted(d->seg, d->nseg, nrun ? run : NULL, nrun, d->tcp_payload,
+                           d->tcp_payload_ref, m, handled, rco);
     const double t3 = mono_ms();
     delivered += deliver_burst(m, k, v, rco, handled);
     g_udp_done = 0;
@@ -2754,12 +2859,32 @@ int64_t nstack_drain_all_sum(void *buf, size_t cap, uint64_t *bytes, uint64_t *s
     return drain_impl(buf, cap, bytes, sum);
 }
 
+int nstack_set_rx_gro(uint32_t W) {
+    if (W > RXG_GRO_MAX_WINDOW) return RXG_EINVAL;
+    pthread_mutex_lock(&g_lock);
+    int rc = W && g_inplace ? RXG_EINVAL : RXG_OK; /* (payloads left in their frames) */
+    if (rc == RXG_OK) {
+        g_gro = W;
+        if (g_ctx && !g_inplace) rc = rxg_tune_deliver(g_ctx, W ? RXG_DLV_TCP_GRO : 0u);
+        if (g_ctx && W && rc == RXG_OK) rc = rxg_tune_gro(g_ctx, W);
+    }
+    pthread_mutex_unlock(&g_lock);
+    return rc;
+}
+
 int nstack_set_rx_inplace(int on, void (*release)(rxg_mbuf *m, void *arg), void *arg) {
     pthread_mutex_lock(&g_lock);
+    if (on && g_gro) { /* (coalesced payloads are gathered, not left in place) */
+        pthread_mutex_unlock(&g_lock);
+        return RXG_EINVAL;
+    }
     g_inplace = on != 0;
     g_mb_release = release;
     g_mb_arg = arg;
-    const int rc = g_ctx ? rxg_tune_deliver(g_ctx, g_inplace ? RXG_DLV_TCP_IN_PLACE : 0u) : RXG_OK;
+    const int rc = g_ctx ? rxg_tune_deliver(g_ctx, g_inplace ? RXG_DLV_TCP_IN_PLACE
+                                                   : g_gro   ? RXG_DLV_TCP_GRO
+                                                             : 0u)
+                         : RXG_OK;
     pthread_mutex_unlock(&g_lock);
     return rc;
 }
@@ -3207,7 +3332,13 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
 }
 
 uint64_t nstack_stat(int which) {
-    if (which < 0 || which > 14) return 0;
+    if (which < 0 || which > 15) return 0;
+    if (which == 15) { /* segments absorbed by receive coalescing */
+        pthread_mutex_lock(&g_lock);
+        const uint64_t a = g_gro_absorbed;
+        pthread_mutex_unlock(&g_lock);
+        return a;
+    }
     if (which == 14) return (uint64_t)atomic_load_explicit(&g_tso_frags, memory_order_relaxed);
     if (which == 13) return (uint64_t)atomic_load_explicit(&g_txe_frames, memory_order_relaxed);
     if (which == 12) return (uint64_t)atomic_load_explicit(&g_deliveries, memory_order_acquire);

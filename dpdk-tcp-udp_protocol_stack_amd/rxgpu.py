@@ -107,6 +107,11 @@ SEGMENT_DTYPE = np.dtype([("frame", "<u4"), ("flow", "<u4"), ("seq", "<u4"), ("a
                           ("plen", "<i4"), ("offset", "<u4"), ("sport", "<u2"), ("dport", "<u2"),
                           ("ncopy", "<u2"), ("flags", "u1"), ("hl", "u1")])
 assert SEGMENT_DTYPE.itemsize == 32
+# rxg_tcp_run, a run of receive coalescing (rxg_tcp_coalesce_dev / rxg_tcp_runs_host)
+TCP_RUN_DTYPE = np.dtype([("first", "<u4"), ("nseg", "<u4"), ("bytes", "<u4"), ("offset", "<u4")])
+assert TCP_RUN_DTYPE.itemsize == 16
+GRO_MAX_WINDOW, GRO_DEFAULT_WINDOW = 1 << 20, 65536
+DLV_TCP_IN_PLACE, DLV_TCP_GRO = 0x1, 0x2
 # rxg_txd, the send descriptor of the TX encoder (K5): sip/dip/sport/dport/
 # window/urp raw as the reference stores them, seq/ack host order
 TXD_DTYPE = np.dtype([("dst_mac", "u1", (6,)), ("src_mac", "u1", (6,)), ("sip", "<u4"), ("dip", "<u4"),
@@ -175,6 +180,12 @@ _udp_compact_dev = _sig("rxg_udp_compact_dev", _i32, _vp, _vp, _vp, _vp, _u32, _
 _flows_rebuilds = _sig("rxg_flows_rebuilds", _u32, _vp)
 _tcp_compact_dev = _sig("rxg_tcp_compact_dev", _i32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp,
                         _u64, _vp, _vp)
+_tcp_coalesce_dev = _sig("rxg_tcp_coalesce_dev", _i32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp,
+                         _vp, _vp, _u64, _vp, _vp)
+_tcp_runs_host = _sig("rxg_tcp_runs_host", _i32, _vp, _vp, _u32, _u32, _vp, C.POINTER(_u32))
+_tune_deliver = _sig("rxg_tune_deliver", _i32, _vp, _u32)
+_tune_gro = _sig("rxg_tune_gro", _i32, _vp, _u32)
+_delivery_runs = _sig("rxg_delivery_runs", _i32, _vp, _vp, C.POINTER(_vp), C.POINTER(_u32))
 _process_mbufs_deliver = _sig("rxg_process_mbufs_deliver", _i32, _vp, _vp, _u32, _vp, _vp, _vp)
 _deliver_submit = _sig("rxg_deliver_submit", _i32, _vp, _vp, _u32, _vp, _vp)
 _tune_ingest = _sig("rxg_tune_ingest", _i32, _vp, _u32)
@@ -259,7 +270,9 @@ GROUP_ID_BYTES = 128
 EXPORTED = ["rxg_open", "rxg_close", "rxg_strerror", "rxg_last_hip_error", "rxg_flows_sync",
             "rxg_flows_add", "rxg_flows_remove", "rxg_flows_update_udp", "rxg_flows_update_tcb",
             "rxg_flows_commit", "rxg_num_udp_ids", "rxg_flows_rebuilds", "rxg_udp_compact_dev",
-            "rxg_process_mbufs_udp", "rxg_tcp_compact_dev", "rxg_process_mbufs_deliver",
+            "rxg_process_mbufs_udp", "rxg_tcp_compact_dev", "rxg_tcp_coalesce_dev",
+            "rxg_tcp_runs_host", "rxg_tune_deliver", "rxg_tune_gro", "rxg_delivery_runs",
+            "rxg_process_mbufs_deliver",
             "rxg_deliver_submit", "rxg_deliver_wait", "rxg_tune_ingest",
             "rxg_register_host", "rxg_unregister_host", "rxg_payload_hold", "rxg_payload_release",
             "rxg_classify_dev", "rxg_classify_dev_cs", "rxg_classify_dev8", "rxg_classify", "rxg_classify_span", "rxg_process_mbufs", "rxg_flow_counts",
@@ -499,6 +512,35 @@ class Context:
         _check(_tcp_compact_dev(self._h, p(d_pkts), p(d_off), p(d_len), n, off_unit_log2, p(d_v),
                                 p(d_seg), p(d_payload), payload_cap, p(d_totals), stream),
                "rxg_tcp_compact_dev")
+
+    def tcp_coalesce_dev(self, d_pkts, d_off, d_len, n: int, off_unit_log2: int, d_v, window: int,
+                         d_seg, d_run, d_payload, payload_cap: int, d_totals, stream=None):
+        """K4 with receive coalescing: the sorted segments' in-sequence trains
+        laid down as contiguous runs (rxg_tcp_coalesce_dev), async on stream"""
+        def p(x):
+            return x if (x is None or isinstance(x, int)) else x.data_ptr()
+        _check(_tcp_coalesce_dev(self._h, p(d_pkts), p(d_off), p(d_len), n, off_unit_log2, p(d_v),
+                                 window, p(d_seg), p(d_run), p(d_payload), payload_cap,
+                                 p(d_totals), stream), "rxg_tcp_coalesce_dev")
+
+    def tune_deliver(self, flags: int):
+        """rxg_tune_deliver: DLV_TCP_IN_PLACE or DLV_TCP_GRO (0 = the default)"""
+        _check(_tune_deliver(self._h, flags), "rxg_tune_deliver")
+
+    def tune_gro(self, window: int):
+        """rxg_tune_gro: the coalescing window in bytes (0 = GRO_DEFAULT_WINDOW)"""
+        _check(_tune_gro(self._h, window), "rxg_tune_gro")
+
+    def delivery_runs(self, handle) -> np.ndarray:
+        """rxg_delivery_runs of a waited-for deliver_submit handle: a copy of the
+        burst's runs (empty with DLV_TCP_GRO off)"""
+        _, _, d = handle
+        ptr, n = _vp(), _u32()
+        _check(_delivery_runs(self._h, C.byref(d), C.byref(ptr), C.byref(n)), "rxg_delivery_runs")
+        if not ptr.value or not n.value:
+            return np.zeros(0, TCP_RUN_DTYPE)
+        return np.frombuffer((C.c_uint8 * (16 * n.value)).from_address(ptr.value),
+                             np.uint8).copy().view(TCP_RUN_DTYPE)
 
     def register_host(self, ptr: int, nbytes: int):
         """rxg_register_host: frames in [ptr, ptr + nbytes) are pulled by the
@@ -750,6 +792,19 @@ def tx_tso_count(txd: np.ndarray, mss: int):
     return e.value, b.value
 
 
+def tcp_runs_host(seg: np.ndarray, sip: np.ndarray, window: int) -> np.ndarray:
+    """rxg_tcp_runs_host: the runs of receive coalescing over K4's records (seg,
+    SEGMENT_DTYPE) and their raw source addresses, on the CPU"""
+    seg = np.ascontiguousarray(seg, SEGMENT_DTYPE)
+    sip = np.ascontiguousarray(sip, np.uint32)
+    assert len(seg) == len(sip)
+    run = np.zeros(max(len(seg), 1), TCP_RUN_DTYPE)
+    nrun = _u32()
+    _check(_tcp_runs_host(seg.ctypes.data if len(seg) else None, sip.ctypes.data if len(seg) else None,
+                          len(seg), window, run.ctypes.data, C.byref(nrun)), "rxg_tcp_runs_host")
+    return run[:nrun.value].copy()
+
+
 def tx_encode_tso_host(txd: np.ndarray, payload: np.ndarray, mss: int, cap_bytes: int, out_cap: int,
                        slot_bytes: int = 0, flags: int = 0, fill: int = 0, fill_entries: int = 0):
     """rxg_tx_encode_tso_host, the TX encoder with TCP segmentation on the CPU:
@@ -933,7 +988,8 @@ class NStack:
                    ("nstack_arp_insert", _i32, [_u32, _vp]),
                    ("nstack_tx_burst", _i32, [_vp, _u64, _vp, _vp, _u32, _i32, _vp]),
                    ("nstack_set_tx_encode", _i32, [_i32]),
-                   ("nstack_set_tx_mss", _i32, [_u32])]
+                   ("nstack_set_tx_mss", _i32, [_u32]),
+                   ("nstack_set_rx_gro", _i32, [_u32])]
             for name, res, args in sig:
                 f = getattr(lib, name)
                 f.restype, f.argtypes = res, args
@@ -1236,6 +1292,12 @@ class NStack:
         of 4; 0 = off) as MSS-sized frames"""
         _check(self.lib.nstack_set_tx_mss(mss), "nstack_set_tx_mss")
         return 0
+
+    def set_rx_gro(self, window: int):
+        """nstack_set_rx_gro: a connection's in-sequence PSH|ACK trains arrive as
+        one receive fragment and one ACK per run of at most about `window` bytes
+        (0 = off); raises RxgError (RXG_EINVAL) while in-place receive is on"""
+        _check(self.lib.nstack_set_rx_gro(window), "nstack_set_rx_gro")
 
     def tx_burst(self, max_frames: int = 256, cap_bytes: int = 1 << 20, cksum: bool = False):
         """one udp_out + tcp_out pass: the frames (bytes) it produced"""

@@ -239,6 +239,28 @@ int64_t nstack_drain_all_sum(void *buf, size_t cap, uint64_t *bytes, uint64_t *s
  * returns (nstack_mbufs_put); an mbuf's frame must stay in place until its
  * count is 0. */
 int nstack_set_rx_inplace(int on, void (*release)(rxg_mbuf *m, void *arg), void *arg);
+/* TCP receive coalescing (GRO; the receive side's counterpart of
+ * nstack_set_tx_mss).  W == 0 (the default): a connection's segments of a
+ * burst make one receive fragment and one ACK each.  W != 0 (bytes, at most
+ * RXG_GRO_MAX_WINDOW, else RXG_EINVAL): the GPU runs the coalescing form of
+ * the segment sort (RXG_DLV_TCP_GRO, rxg_tune_gro(W); the rule: rxgpu.h, "TCP
+ * receive coalescing") and an ESTABLISHED connection's run of k > 1
+ * in-sequence PSH|ACK segments makes one receive fragment of the run's bytes —
+ * pointing into the held pooled payload buffer when there is one, copied
+ * otherwise — and one ACK: rcv_nxt advances by the run's bytes, snd_nxt
+ * becomes the run's ack, and the ACK's acknum is rcv_nxt after the run, the
+ * ACK that closes the run in the segment-by-segment order.  Every frame of
+ * the run is handled with rc 0.  The bytes a connection receives and their
+ * order are unchanged; only the count of fragments and ACKs carrying them
+ * drops.  Runs of one, and connections on the frame-by-frame path (LISTEN,
+ * SYN_RCVD, LAST_ACK), go as before.  A full receive ring drops whole runs
+ * (where it would have dropped single segments).  The host-verdict path
+ * (nstack_deliver) computes the runs with rxg_tcp_runs_host; the halves and the
+ * pipelined nstack_rx_submit / nstack_rx_complete paths honour the option.
+ * Not with in-place receive: RXG_EINVAL while nstack_set_rx_inplace is on,
+ * and nstack_set_rx_inplace(on) is RXG_EINVAL while W != 0.  nstack_stat(15)
+ * counts the segments absorbed into a preceding segment's fragment. */
+int nstack_set_rx_gro(uint32_t W);
 /* Items the application has read (fragments, datagram batches) are handed
  * back to the protocol thread and freed by its next nstack_rx_burst (while
  * that burst is on the GPU) / nstack_tx_burst / nstack_deliver call (or
@@ -288,7 +310,8 @@ int nstack_set_halves(uint32_t min_half);
  * items in its next nstack_drain_all (bumped with release order after the
  * deliveries, read with acquire); 13 = frames produced by the TX encoder
  * (nstack_set_tx_encode); 14 = fragments sent as more than one frame in a
- * pass (nstack_set_tx_mss).  Counter 1 also counts TX items dropped (a
+ * pass (nstack_set_tx_mss); 15 = segments absorbed into a preceding segment's
+ * receive fragment (nstack_set_rx_gro).  Counter 1 also counts TX items dropped (a
  * send ring full, or a datagram too long for a frame). */
 uint64_t nstack_stat(int which);
 

@@ -389,6 +389,60 @@ int rxg_tcp_compact_dev(rxg_ctx *ctx, const uint8_t *d_pkts, const uint32_t *d_o
                         const rxg_verdict *d_v, rxg_segment *d_seg, uint8_t *d_payload,
                         uint64_t payload_cap, uint32_t *d_totals, void *stream);
 
+/* ---- TCP receive coalescing (GRO): the receive side's counterpart of TSO
+ * After the sort a connection's segments are adjacent.  The coalescing form of
+ * K4 recognises the in-sequence trains among them and lays each train's
+ * payload down as one contiguous byte range, so the host queues one receive
+ * fragment and one ACK per train instead of one per segment.  Only PSH|ACK
+ * segments merge: only PSH segments deliver data here, as in the reference
+ * (tcp.c:226-262), so merging never changes which bytes a connection
+ * receives, only how many fragments and ACKs carry them.  The rule, on the
+ * sorted records seg[0..nseg) and each record's raw source address sip (frame
+ * bytes 26-29, 0 past the capture):
+ *   mergeable(j): flags == 0x18 (PSH|ACK exactly), hl == 5, plen > 0 and
+ *                 ncopy == plen (the payload was captured whole);
+ *   j links to j-1: both mergeable; flow, sip, sport, dport and ack equal;
+ *                 seq[j] == seq[j-1] + plen[j-1] (mod 2^32);
+ *   a chain is a maximal range of consecutive records in which every record
+ *   but the first links to its predecessor; b[j] = the 64-bit sum of plen
+ *   over the chain's records before j; with the window W (bytes, 1 ..
+ *   RXG_GRO_MAX_WINDOW) record j starts a new run iff it starts its chain or
+ *   b[j] / W != b[j-1] / W.
+ * The runs partition [0, nseg) in order; a record that is not mergeable is a
+ * run of one; a run's payload is less than W + 65536 bytes.  Out-of-order
+ * segments are not reordered and segments with TCP options never merge. */
+typedef struct rxg_tcp_run {
+    uint32_t first;  /* index of the run's first record */
+    uint32_t nseg;   /* records in the run */
+    uint32_t bytes;  /* sum of their ncopy */
+    uint32_t offset; /* the run's start in the payload buffer (16-B aligned) */
+} rxg_tcp_run;       /* 16 bytes */
+#define RXG_GRO_MAX_WINDOW (1u << 20)
+#define RXG_GRO_DEFAULT_WINDOW 65536u
+/* rxg_tcp_compact_dev with coalescing, asynchronous on `stream`.  d_seg gets
+ * field for field what rxg_tcp_compact_dev writes for the same inputs, except
+ * offset: the first segment of a run sits at the run's offset and each later
+ * one follows its predecessor byte-contiguously (no padding inside a run).
+ * d_run (room for n) gets the runs in order, laid out one after the other,
+ * each starting at the 16-B-rounded end of the one before.  d_totals (4
+ * words) = {segments, payload bytes used (the 16-B-rounded end of the last
+ * run), 1 if payload_cap was too small, runs}.  The bytes from a run's end to
+ * its 16-B-rounded end are written as 0; a run that would pass payload_cap
+ * sets the overflow flag and is not written; no other byte of d_payload is
+ * touched.  d_payload is required (NULL: RXG_EINVAL), W outside 1 ..
+ * RXG_GRO_MAX_WINDOW is RXG_EINVAL.  n == 0 or an empty tcb id space zeroes
+ * the totals.  The device workspace grows on demand (stream-ordered). */
+int rxg_tcp_coalesce_dev(rxg_ctx *ctx, const uint8_t *d_pkts, const uint32_t *d_off,
+                         const uint16_t *d_len, uint32_t n, uint32_t off_unit_log2,
+                         const rxg_verdict *d_v, uint32_t W, rxg_segment *d_seg, rxg_tcp_run *d_run,
+                         uint8_t *d_payload, uint64_t payload_cap, uint32_t *d_totals, void *stream);
+/* The same rule on records in host memory (no device, no context): run (room
+ * for nseg) gets the runs, offset as the device lays them out, *nrun their
+ * count.  seg[].offset is neither read nor modified.  The CPU path and the
+ * tests' second opinion; the device calls never fall back to it. */
+int rxg_tcp_runs_host(const rxg_segment *seg, const uint32_t *sip, uint32_t nseg, uint32_t W,
+                      rxg_tcp_run *run, uint32_t *nrun);
+
 /* One mbuf burst through the whole device half of delivery: classify
  * (rxg_process_mbufs), then the UDP compaction (when the UDP id space is at
  * most RXG_COMPACT_MAX_FLOWS; else dgram/first are NULL and ndgram 0) and
@@ -446,7 +500,20 @@ int rxg_deliver_wait(rxg_ctx *ctx, rxg_delivery *d, float ms[8]);
  * offset in its frame (34 + 4*hl; ncopy captured bytes).  The caller keeps
  * the frames in place for as long as it points into them. */
 #define RXG_DLV_TCP_IN_PLACE 0x1u
+/* RXG_DLV_TCP_GRO: the TCP half of a delivery burst runs the coalescing form
+ * of K4 (rxg_tcp_coalesce_dev) with the window of rxg_tune_gro (W bytes; 0
+ * restores the default, RXG_GRO_DEFAULT_WINDOW): the records' offsets are
+ * byte-contiguous inside a run, and the runs cross PCIe with the records
+ * (rxg_delivery_runs).  The pooled payload buffers work unchanged.  Not with
+ * RXG_DLV_TCP_IN_PLACE (RXG_EINVAL): payloads that stay in their frames
+ * cannot be made contiguous.  Off by default. */
+#define RXG_DLV_TCP_GRO 0x2u
 int rxg_tune_deliver(rxg_ctx *ctx, uint32_t flags);
+int rxg_tune_gro(rxg_ctx *ctx, uint32_t W);
+/* The runs of a waited-for delivery burst: *run / *nrun, valid as long as the
+ * burst's delivery set is; NULL / 0 when RXG_DLV_TCP_GRO was off for it. */
+int rxg_delivery_runs(rxg_ctx *ctx, const rxg_delivery *d, const rxg_tcp_run **run,
+                      uint32_t *nrun);
 
 /* Keep a burst's TCP payload buffer (rxg_delivery.tcp_payload_ref) alive past
  * the context's next burst call — e.g. while receive fragments that point into
