@@ -73,6 +73,11 @@ hipError_t rx_gro_launch(const uint8_t *pkts, const uint32_t *off, const uint16_
                          uint32_t unit_log2, const uint4 *verd, uint32_t nt, uint32_t W,
                          rxg_segment *seg, rxg_tcp_run *run, uint8_t *payload, uint64_t cap,
                          uint32_t *totals, void *ws, hipStream_t s);
+size_t rx_order_ws_bytes(uint32_t n);
+hipError_t rx_order_launch(const uint8_t *pkts, const uint32_t *off, const uint16_t *len, uint32_t n,
+                           uint32_t unit_log2, const uint4 *verd, uint32_t nt, uint32_t W,
+                           rxg_segment *seg, rxg_tcp_run *run, uint8_t *payload, uint64_t cap,
+                           uint32_t *totals, void *ws, hipStream_t s);
 size_t rx_compact_ws_bytes(uint32_t n, uint32_t nflows);
 hipError_t rx_compact_launch(const uint8_t *pkts, const uint32_t *off, const uint16_t *len,
                              uint32_t n, uint32_t unit_log2, const uint4 *verd, uint32_t nflows,
@@ -294,8 +299,9 @@ struct rxg_ctx {
     // device buffers are shared: every step runs on `stream`, in order) and its
     // phase events; a set's results stay valid until the set is reused
     struct delivery_set {
-        bool on = false, udp = false, tcp = false, gro = false;
+        bool on = false, udp = false, tcp = false, gro = false, order = false;
         uint32_t nrun = 0;             // (rxg_delivery_runs)
+        uint32_t moved = 0;            // (rxg_delivery_moved)
         rxg_tcp_run *h_ss_run = nullptr;
         uint64_t ticket = 0;
         double t0 = 0, t1 = 0;
@@ -1168,7 +1174,8 @@ int rxg_tune_tables(rxg_ctx *c, uint32_t flags) {
 }
 
 int rxg_tune_deliver(rxg_ctx *c, uint32_t flags) {
-    if (!c || (flags & ~(RXG_DLV_TCP_IN_PLACE | RXG_DLV_TCP_GRO))) return RXG_EINVAL;
+    if (!c || (flags & ~(RXG_DLV_TCP_IN_PLACE | RXG_DLV_TCP_GRO | RXG_DLV_TCP_ORDER)))
+        return RXG_EINVAL;
     // (payloads that stay in their frames cannot be made contiguous)
     if ((flags & RXG_DLV_TCP_IN_PLACE) && (flags & RXG_DLV_TCP_GRO)) return RXG_EINVAL;
     c->deliver_flags = flags;
@@ -1774,6 +1781,22 @@ static int gro_impl(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off, co
     return RXG_OK;
 }
 
+// K4 or its coalescing form (W != 0) on the sequence-ordered segments
+// (rx_segsort.hip); the workspace is K4's, grown
+static int order_impl(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off, const uint16_t *d_len,
+                      uint32_t n, uint32_t off_unit_log2, const uint4 *d_v, uint32_t W,
+                      rxg_segment *d_seg, rxg_tcp_run *d_run, uint8_t *d_payload, uint64_t cap,
+                      uint32_t *d_totals, hipStream_t s) {
+    const size_t ws = rx_order_ws_bytes(n);
+    if (ws > c->d_ss_ws_cap) {
+        int rc = ensure_dev_async(&c->d_ss_ws, &c->d_ss_ws_cap, ws, s);
+        if (rc) return rc;
+    }
+    HIPCHK(rx_order_launch(d_pkts, d_off, d_len, n, off_unit_log2, d_v, c->fs.tcp.id_space(), W,
+                           d_seg, d_run, d_payload, cap, d_totals, c->d_ss_ws, s));
+    return RXG_OK;
+}
+
 int rxg_payload_hold(rxg_ctx *c, int32_t ref) {
     if (!c || ref < 0 || ref >= RXG_PAYLOAD_BUFS) return RXG_EINVAL;
     c->pl[ref].refs.fetch_add(1, std::memory_order_acq_rel);
@@ -1813,6 +1836,32 @@ int rxg_tcp_coalesce_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_of
     DEVGUARD(c);
     return gro_impl(c, d_pkts, d_off, d_len, n, off_unit_log2, reinterpret_cast<const uint4 *>(d_v), W,
                     d_seg, d_run, d_payload, payload_cap, d_totals, (hipStream_t)stream);
+}
+
+int rxg_tcp_compact_ordered_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off,
+                                const uint16_t *d_len, uint32_t n, uint32_t off_unit_log2,
+                                const rxg_verdict *d_v, uint32_t W, rxg_segment *d_seg,
+                                rxg_tcp_run *d_run, uint8_t *d_payload, uint64_t payload_cap,
+                                uint32_t *d_totals, void *stream) {
+    if (!c) return RXG_EINVAL;
+    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
+    if (!d_totals || (n && (!d_pkts || !d_off || !d_len || !d_v || !d_seg))) return RXG_EINVAL;
+    // (W == 0: K4's rules, d_payload null = records only; else the coalescing call's)
+    if (W > RXG_GRO_MAX_WINDOW || (W && (!d_payload || (n && !d_run)))) return RXG_EINVAL;
+    if (off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
+    DEVGUARD(c);
+    return order_impl(c, d_pkts, d_off, d_len, n, off_unit_log2, reinterpret_cast<const uint4 *>(d_v),
+                      W, d_seg, d_run, d_payload, payload_cap, d_totals, (hipStream_t)stream);
+}
+
+int rxg_delivery_moved(rxg_ctx *c, const rxg_delivery *d, uint32_t *moved) {
+    if (!c || !d || !moved) return RXG_EINVAL;
+    *moved = 0;
+    if (d->set < 1 || d->set > RXG_DELIVER_DEPTH) return RXG_EINVAL;
+    const rxg_ctx::delivery_set &ds = c->dls[d->set - 1];
+    if (ds.on) return RXG_EINVAL; // (not waited for yet)
+    if (ds.order) *moved = ds.moved;
+    return RXG_OK;
 }
 
 int rxg_delivery_runs(rxg_ctx *c, const rxg_delivery *d, const rxg_tcp_run **run, uint32_t *nrun) {
@@ -1865,12 +1914,13 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
     if (!ds.h_ss_totals) {
         if (!c->d_ss_seg) HIPCHK(hipMalloc(&c->d_ss_seg, (size_t)c->max_pkts * sizeof(rxg_segment)));
         if (!c->d_ss_payload) HIPCHK(hipMalloc(&c->d_ss_payload, c->max_bytes));
-        if (!c->d_ss_totals) HIPCHK(hipMalloc(&c->d_ss_totals, 4 * sizeof(uint32_t)));
+        if (!c->d_ss_totals) HIPCHK(hipMalloc(&c->d_ss_totals, 5 * sizeof(uint32_t)));
         if (!ds.h_ss_seg)
             HIPCHK(hipHostMalloc((void **)&ds.h_ss_seg, (size_t)c->max_pkts * sizeof(rxg_segment), 0));
-        HIPCHK(hipHostMalloc((void **)&ds.h_ss_totals, 4 * sizeof(uint32_t), 0));
+        HIPCHK(hipHostMalloc((void **)&ds.h_ss_totals, 5 * sizeof(uint32_t), 0));
     }
     const bool gro = (c->deliver_flags & RXG_DLV_TCP_GRO) != 0;
+    const bool order = (c->deliver_flags & RXG_DLV_TCP_ORDER) != 0;
     if (gro) {
         if (!c->d_ss_run) HIPCHK(hipMalloc(&c->d_ss_run, (size_t)c->max_pkts * sizeof(rxg_tcp_run)));
         if (!ds.h_ss_run)
@@ -1910,8 +1960,8 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
         d->udp_payload = ds.h_cp_payload;
         memset(ds.h_cp_first, 0, (nf + 1) * sizeof(uint32_t));
     }
-    ds.on = ds.udp = ds.tcp = ds.gro = false;
-    ds.nrun = 0;
+    ds.on = ds.udp = ds.tcp = ds.gro = ds.order = false;
+    ds.nrun = ds.moved = 0;
     ds.ticket = 0;
     ds.t0 = t0;
     c->dl_next = (si + 1) % RXG_DELIVER_DEPTH;
@@ -1939,7 +1989,13 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
                                    c->stream)))
                 return rc;
         tcp = c->fs.tcp.id_space() > 0;
-        if (tcp && gro) {
+        if (tcp && order) {
+            if ((rc = order_impl(c, sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, sl.d_out,
+                                 gro ? c->gro_window : 0u, c->d_ss_seg, c->d_ss_run,
+                                 inplace ? nullptr : c->d_ss_payload, c->max_bytes, c->d_ss_totals,
+                                 c->stream)))
+                return rc;
+        } else if (tcp && gro) {
             if ((rc = gro_impl(c, sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, sl.d_out, c->gro_window,
                                c->d_ss_seg, c->d_ss_run, c->d_ss_payload, c->max_bytes,
                                c->d_ss_totals, c->stream)))
@@ -1967,7 +2023,8 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
                                   c->stream));
         }
         if (tcp) {
-            HIPCHK(hipMemcpyAsync(ds.h_ss_totals, c->d_ss_totals, (gro ? 4 : 3) * sizeof(uint32_t),
+            HIPCHK(hipMemcpyAsync(ds.h_ss_totals, c->d_ss_totals,
+                                  (order ? 5 : gro ? 4 : 3) * sizeof(uint32_t),
                                   hipMemcpyDeviceToHost, c->stream));
             if (gro) // (the runs cross with the records: at most n of them)
                 HIPCHK(hipMemcpyAsync(ds.h_ss_run, c->d_ss_run, (size_t)n * sizeof(rxg_tcp_run),
@@ -1991,6 +2048,7 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
     ds.udp = udp;
     ds.tcp = tcp;
     ds.gro = tcp && gro;
+    ds.order = tcp && order;
     ds.ticket = t;
     ds.t1 = t1;
     return RXG_OK;
@@ -2016,6 +2074,7 @@ int rxg_deliver_wait(rxg_ctx *c, rxg_delivery *d, float ms[8]) {
     if (udp) d->ndgram = ds.h_cp_totals[0], d->udp_bytes = ds.h_cp_totals[1];
     if (tcp) d->nseg = ds.h_ss_totals[0], d->tcp_bytes = ds.h_ss_totals[1];
     if (ds.gro) ds.nrun = ds.h_ss_totals[3];
+    if (ds.order) ds.moved = ds.h_ss_totals[4];
     if (ms) {
         ms[0] = (float)(ds.t1 - ds.t0);
         for (int k = 0; k < 4; ++k) HIPCHK(hipEventElapsedTime(&ms[k + 1], ds.tev[k], ds.tev[k + 1]));

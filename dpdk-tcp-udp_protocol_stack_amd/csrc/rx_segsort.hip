@@ -731,3 +731,284 @@ hipError_t rx_gro_launch(const uint8_t *pkts, const uint32_t *off, const uint16_
                        payload, cap, totals);
     return hipGetLastError();
 }
+
+// ---- Sequence ordering (opt-in): a permutation stage between the sort and
+// the record stage (the rule: include/rxgpu.h, "TCP sequence ordering";
+// restated on the host in rx_order_host.cpp).  On the sorted (flow, frame)
+// arrays:
+//   1. group heads from a comparison with the predecessor, the last head at or
+//      before j by a max scan (block scan + one-block scan of the block maxima);
+//   2. the biased key (seq - seq[head]) ^ 0x80000000 and the burst's "some
+//      inversion" flag (a record below its predecessor inside a group);
+//   3. K4's stable radix passes over (key, position), four digits, then over
+//      the head index of each position (monotone in position, so every group
+//      lands where it was, sorted inside);
+//   4. the (flow, frame) arrays gathered through the permutation, the moved
+//      records counted.
+// The record / copy / coalescing kernels then run unchanged on the permuted
+// arrays.  No group is walked: one connection may own the whole burst.
+namespace {
+
+// what decides a record's group, and its seq
+struct ord_key {
+    uint32_t flow, sip, ports, movable, seq;
+};
+
+// sorted segment j's group key, bytes past the capture read as 0
+// (ss_record_kernel's rule)
+__device__ __forceinline__ ord_key ord_decode(const uint8_t *__restrict__ pkts,
+                                              const uint32_t *__restrict__ off,
+                                              const uint16_t *__restrict__ len, uint32_t unit_log2,
+                                              const uint32_t *__restrict__ keys,
+                                              const uint32_t *__restrict__ vals, uint32_t j) {
+    const uint32_t i = vals[j];
+    const uint8_t *f = pkts + ((uint64_t)off[i] << unit_log2);
+    const uint32_t cap = len[i];
+    auto b = [&](uint32_t q) -> uint32_t { return q < cap ? (uint32_t)f[q] : 0u; };
+    ord_key k;
+    k.flow = keys[j];
+    k.sip = b(26) | (b(27) << 8) | (b(28) << 16) | (b(29) << 24);
+    k.ports = b(34) | (b(35) << 8) | (b(36) << 16) | (b(37) << 24);
+    k.movable = (b(47) & 0x06u) == 0u; // neither SYN nor RST
+    k.seq = (b(38) << 24) | (b(39) << 16) | (b(40) << 8) | b(41);
+    return k;
+}
+
+// round 1: sq[j] = seq; hl[j] = 1 + the last group head at or before j inside
+// the block (0: none yet); bH[block] = the block's last head; bZ[block] = 0
+// (the sum half of gro_scan_kernel runs beside the max half, on zeros)
+__global__ __launch_bounds__(SS_THREADS) void ord_head_kernel(
+    const uint8_t *__restrict__ pkts, const uint32_t *__restrict__ off,
+    const uint16_t *__restrict__ len, uint32_t unit_log2, const uint32_t *__restrict__ keys,
+    const uint32_t *__restrict__ vals, const uint32_t *__restrict__ totals,
+    uint32_t *__restrict__ sq, uint32_t *__restrict__ hl, uint64_t *__restrict__ bH,
+    uint64_t *__restrict__ bZ) {
+    __shared__ uint32_t pf[SS_THREADS + 1u], ps[SS_THREADS + 1u], pp[SS_THREADS + 1u],
+        pm[SS_THREADS + 1u];
+    __shared__ uint32_t ws[SS_THREADS / 64u];
+    const uint32_t nseg = totals[0];
+    const uint32_t t = threadIdx.x;
+    const uint32_t j0 = blockIdx.x * SS_THREADS, j = j0 + t;
+    if (j0 >= nseg) return; // (uniform)
+    ord_key k = {0u, 0u, 0u, 0u, 0u};
+    if (j < nseg) k = ord_decode(pkts, off, len, unit_log2, keys, vals, j);
+    pf[t + 1u] = k.flow, ps[t + 1u] = k.sip, pp[t + 1u] = k.ports, pm[t + 1u] = k.movable;
+    if (t == 0u) { // the block's predecessor record, decoded again
+        ord_key p = {0u, 0u, 0u, 0u, 0u};
+        if (j0) p = ord_decode(pkts, off, len, unit_log2, keys, vals, j0 - 1u);
+        pf[0] = p.flow, ps[0] = p.sip, pp[0] = p.ports, pm[0] = p.movable;
+    }
+    __syncthreads();
+    const bool head = !j || !k.movable || !pm[t] || pf[t] != k.flow || ps[t] != k.sip ||
+                      pp[t] != k.ports;
+    uint32_t hmax;
+    const uint32_t hinc = gro_block_scan<true>((j < nseg && head) ? j + 1u : 0u, ws, hmax);
+    if (j < nseg) {
+        sq[j] = k.seq;
+        hl[j] = hinc;
+    }
+    if (t == 0u) {
+        bH[blockIdx.x] = hmax;
+        bZ[blockIdx.x] = 0u;
+    }
+}
+
+// round 2 (bH scanned), all n positions: the radix key, the head index and
+// the position itself; the positions past the delivered segments are groups
+// of one, so they stay where they are; *flag is set when a record's key is
+// below its predecessor's inside a group (else the permutation is the identity)
+__global__ __launch_bounds__(SS_THREADS) void ord_key_kernel(
+    const uint32_t *__restrict__ totals, uint32_t n, const uint32_t *__restrict__ sq,
+    const uint32_t *__restrict__ hl, const uint64_t *__restrict__ bH, uint32_t *__restrict__ ok,
+    uint32_t *__restrict__ hk, uint32_t *__restrict__ pos, uint32_t *__restrict__ flag) {
+    const uint32_t nseg = totals[0];
+    const uint32_t j = blockIdx.x * SS_THREADS + threadIdx.x;
+    bool inv = false;
+    if (j < n) {
+        uint32_t key = 0u, h = j;
+        if (j < nseg) {
+            // the group's head: inside the block, else the last one of the
+            // blocks before (record 0 heads a group, so there is one)
+            const uint32_t l = hl[j];
+            h = (l ? l : (uint32_t)bH[blockIdx.x]) - 1u;
+            const uint32_t s0 = sq[h];
+            key = (sq[j] - s0) ^ 0x80000000u;
+            inv = h != j && key < ((sq[j - 1u] - s0) ^ 0x80000000u);
+        }
+        ok[j] = key;
+        hk[j] = h;
+        pos[j] = j;
+    }
+    const uint64_t m = __ballot(inv);
+    if (m && (threadIdx.x & 63u) == (uint32_t)__ffsll((unsigned long long)m) - 1u) atomicOr(flag, 1u);
+}
+
+// between the key passes and the head passes: the radix key of position k
+// becomes the head index of the record now there
+__global__ __launch_bounds__(SS_THREADS) void ord_headkey_kernel(uint32_t n,
+                                                                const uint32_t *__restrict__ flag,
+                                                                const uint32_t *__restrict__ hk,
+                                                                const uint32_t *__restrict__ pos,
+                                                                uint32_t *__restrict__ key) {
+    if (!flag[0]) return; // (uniform) no inversion: ord_apply_kernel takes the identity
+    const uint32_t k = blockIdx.x * SS_THREADS + threadIdx.x;
+    if (k < n) key[k] = hk[pos[k]];
+}
+
+// the sorted (flow, frame) arrays through the permutation (the identity when
+// no inversion was seen), and totals[4] = the records that moved
+__global__ __launch_bounds__(SS_THREADS) void ord_apply_kernel(
+    uint32_t n, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ perm,
+    const uint32_t *__restrict__ kin, const uint32_t *__restrict__ vin,
+    uint32_t *__restrict__ kout, uint32_t *__restrict__ vout, uint32_t *__restrict__ totals) {
+    const uint32_t nseg = totals[0];
+    const uint32_t k = blockIdx.x * SS_THREADS + threadIdx.x;
+    bool mv = false;
+    if (k < n) {
+        const uint32_t p = flag[0] ? perm[k] : k;
+        kout[k] = kin[p];
+        vout[k] = vin[p];
+        mv = k < nseg && p != k;
+    }
+    const uint64_t m = __ballot(mv);
+    if (m && (threadIdx.x & 63u) == (uint32_t)__ffsll((unsigned long long)m) - 1u)
+        atomicAdd(&totals[4], (uint32_t)__popcll(m));
+}
+
+} // namespace
+
+// workspace: the coalescing form's, then seven words per frame (seq, local
+// head, head index, and the (key, position) pair twice), two 64-bit block
+// arrays and the flag
+size_t rx_order_ws_bytes(uint32_t n) {
+    const size_t nn = n ? n : 1;
+    return rx_gro_ws_bytes(n) + 7 * ss_align(nn * 4) +
+           2 * ss_align((size_t)(ss_blocks(n) ? ss_blocks(n) : 1) * 8) + 256;
+}
+
+// K4 (W == 0; payload NULL: records only) or its coalescing form (W != 0) on
+// the sequence-ordered segments; d_totals: 5 (segments, payload bytes,
+// overflow flag, runs, moved)
+hipError_t rx_order_launch(const uint8_t *pkts, const uint32_t *off, const uint16_t *len, uint32_t n,
+                           uint32_t unit_log2, const uint4 *verd, uint32_t nt, uint32_t W,
+                           rxg_segment *seg, rxg_tcp_run *run, uint8_t *payload, uint64_t cap,
+                           uint32_t *totals, void *ws, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(totals, 0, 5 * sizeof(uint32_t), s);
+    if (e != hipSuccess || n == 0 || nt == 0) return e;
+    const size_t nn = ss_align((size_t)n * 4);
+    uint8_t *w8 = static_cast<uint8_t *>(ws);
+    uint32_t *ka = reinterpret_cast<uint32_t *>(w8), *va = reinterpret_cast<uint32_t *>(w8 + nn);
+    uint32_t *kb = reinterpret_cast<uint32_t *>(w8 + 2 * nn), *vb = reinterpret_cast<uint32_t *>(w8 + 3 * nn);
+    const uint32_t ntiles = ss_tiles(n), nblk = ss_blocks(n);
+    uint32_t *hist = reinterpret_cast<uint32_t *>(w8 + 4 * nn);
+    uint32_t *tsum = reinterpret_cast<uint32_t *>(w8 + 4 * nn + ss_align((size_t)SS_DIGITS * ntiles * 4));
+    const size_t nb8 = ss_align((size_t)nblk * 8);
+    uint8_t *o8 = w8 + rx_gro_ws_bytes(n);
+    uint32_t *sq = reinterpret_cast<uint32_t *>(o8), *hl = reinterpret_cast<uint32_t *>(o8 + nn);
+    uint32_t *hk = reinterpret_cast<uint32_t *>(o8 + 2 * nn);
+    uint32_t *oka = reinterpret_cast<uint32_t *>(o8 + 3 * nn), *pa = reinterpret_cast<uint32_t *>(o8 + 4 * nn);
+    uint32_t *okb = reinterpret_cast<uint32_t *>(o8 + 5 * nn), *pb = reinterpret_cast<uint32_t *>(o8 + 6 * nn);
+    uint64_t *bH = reinterpret_cast<uint64_t *>(o8 + 7 * nn);
+    uint64_t *bZ = reinterpret_cast<uint64_t *>(o8 + 7 * nn + nb8);
+    uint32_t *flag = reinterpret_cast<uint32_t *>(o8 + 7 * nn + 2 * nb8);
+    if ((e = hipMemsetAsync(flag, 0, sizeof(uint32_t), s)) != hipSuccess) return e;
+    // one stable radix pass of K4's sort over digit `shift` of (ki, vi)
+    auto pass = [&](const uint32_t *ki, const uint32_t *vi, uint32_t shift, uint32_t *ko,
+                    uint32_t *vo) -> hipError_t {
+        hipLaunchKernelGGL(ss_hist_kernel<false>, dim3(ntiles), dim3(SS_THREADS), 0, s, verd, ki, n,
+                           nt, shift, ntiles, hist, totals);
+        hipLaunchKernelGGL(ss_scan_kernel, dim3(1), dim3(1024), 0, s, hist, SS_DIGITS * ntiles,
+                           nullptr);
+        hipLaunchKernelGGL(ss_scatter_kernel<false>, dim3(ntiles), dim3(SS_THREADS), 0, s, verd, ki,
+                           vi, n, nt, shift, ntiles, hist, ko, vo);
+        return hipGetLastError();
+    };
+    // the sort, as in rx_segsort_launch
+    const uint32_t bits = 32u - (uint32_t)__builtin_clz(nt);
+    const uint32_t passes = (bits + 7u) / 8u;
+    const uint32_t *kin = nullptr, *vin = nullptr;
+    uint32_t *kout = ka, *vout = va;
+    for (uint32_t p = 0; p < passes; ++p) {
+        const uint32_t shift = 8u * p;
+        if (p == 0) {
+            hipLaunchKernelGGL(ss_hist_kernel<true>, dim3(ntiles), dim3(SS_THREADS), 0, s, verd,
+                               nullptr, n, nt, shift, ntiles, hist, totals);
+            hipLaunchKernelGGL(ss_scan_kernel, dim3(1), dim3(1024), 0, s, hist, SS_DIGITS * ntiles,
+                               nullptr);
+            hipLaunchKernelGGL(ss_scatter_kernel<true>, dim3(ntiles), dim3(SS_THREADS), 0, s, verd,
+                               nullptr, nullptr, n, nt, shift, ntiles, hist, kout, vout);
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+        } else if ((e = pass(kin, vin, shift, kout, vout)) != hipSuccess) {
+            return e;
+        }
+        kin = kout, vin = vout;
+        kout = (kout == ka) ? kb : ka;
+        vout = (vout == va) ? vb : va;
+    }
+    // the permutation: keys, four key passes (a -> b -> a -> b -> a), the head
+    // index as the key, its passes (positions 0 .. n-1)
+    hipLaunchKernelGGL(ord_head_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, pkts, off, len, unit_log2,
+                       kin, vin, totals, sq, hl, bH, bZ);
+    hipLaunchKernelGGL(gro_scan_kernel, dim3(2), dim3(1024), 0, s, bZ, bH, totals, nullptr);
+    hipLaunchKernelGGL(ord_key_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, totals, n, sq, hl, bH, oka,
+                       hk, pa, flag);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    uint32_t *ok = oka, *pv = pa, *ok2 = okb, *pv2 = pb;
+    for (uint32_t p = 0; p < 4u; ++p) {
+        if ((e = pass(ok, pv, 8u * p, ok2, pv2)) != hipSuccess) return e;
+        uint32_t *x = ok; ok = ok2, ok2 = x;
+        x = pv, pv = pv2, pv2 = x;
+    }
+    hipLaunchKernelGGL(ord_headkey_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, n, flag, hk, pv, ok);
+    const uint32_t hbits = n > 1u ? 32u - (uint32_t)__builtin_clz(n - 1u) : 1u;
+    for (uint32_t p = 0; p < (hbits + 7u) / 8u; ++p) {
+        if ((e = pass(ok, pv, 8u * p, ok2, pv2)) != hipSuccess) return e;
+        uint32_t *x = ok; ok = ok2, ok2 = x;
+        x = pv, pv = pv2, pv2 = x;
+    }
+    hipLaunchKernelGGL(ord_apply_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, n, flag, pv, kin, vin,
+                       kout, vout, totals);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    kin = kout, vin = vout;
+    if (!W) { // K4's record stage, as in rx_segsort_launch
+        if (!payload) {
+            hipLaunchKernelGGL(ss_record_kernel<true>, dim3(nblk), dim3(SS_THREADS), 0, s, pkts, off,
+                               len, unit_log2, kin, vin, totals, seg, tsum);
+            return hipGetLastError();
+        }
+        hipLaunchKernelGGL(ss_record_kernel<false>, dim3(nblk), dim3(SS_THREADS), 0, s, pkts, off,
+                           len, unit_log2, kin, vin, totals, seg, tsum);
+        hipLaunchKernelGGL(ss_scan_kernel, dim3(1), dim3(1024), 0, s, tsum, nblk, totals + 1);
+        hipLaunchKernelGGL(ss_copy_kernel, dim3((uint32_t)(((uint64_t)n + 3) / 4)), dim3(SS_THREADS),
+                           0, s, pkts, off, len, unit_log2, tsum, seg, payload, cap, totals);
+        return hipGetLastError();
+    }
+    // the coalescing stage, as in rx_gro_launch
+    uint8_t *g8 = w8 + rx_segsort_ws_bytes(n);
+    uint32_t *gl = reinterpret_cast<uint32_t *>(g8), *hd = reinterpret_cast<uint32_t *>(g8 + nn);
+    uint32_t *rl = reinterpret_cast<uint32_t *>(g8 + 2 * nn);
+    uint32_t *rfirst = reinterpret_cast<uint32_t *>(g8 + 3 * nn);
+    uint32_t *ol = reinterpret_cast<uint32_t *>(g8 + 4 * nn);
+    uint64_t *bG = reinterpret_cast<uint64_t *>(g8 + 5 * nn);
+    uint64_t *bHg = reinterpret_cast<uint64_t *>(g8 + 5 * nn + nb8);
+    uint64_t *bR = reinterpret_cast<uint64_t *>(g8 + 5 * nn + 2 * nb8);
+    uint64_t *bO = reinterpret_cast<uint64_t *>(g8 + 5 * nn + 3 * nb8);
+    uint64_t *tot = reinterpret_cast<uint64_t *>(g8 + 5 * nn + 4 * nb8); // {sum of ncopy, runs, bytes used}
+    if ((e = hipMemsetAsync(tot, 0, 3 * sizeof(uint64_t), s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(gro_record_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, pkts, off, len,
+                       unit_log2, kin, vin, totals, seg, gl, hd, bG, bHg);
+    hipLaunchKernelGGL(gro_scan_kernel, dim3(2), dim3(1024), 0, s, bG, bHg, totals, tot);
+    hipLaunchKernelGGL(gro_runhead_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, seg, totals, W, gl,
+                       hd, bG, bHg, rl, bR);
+    hipLaunchKernelGGL(gro_scan_kernel, dim3(1), dim3(1024), 0, s, bR, nullptr, totals, tot + 1);
+    hipLaunchKernelGGL(gro_runid_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, totals, tot, rl, bR,
+                       rfirst);
+    hipLaunchKernelGGL(gro_run_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, totals, tot, gl, bG,
+                       rfirst, run, ol, bO);
+    hipLaunchKernelGGL(gro_scan_kernel, dim3(1), dim3(1024), 0, s, bO, nullptr,
+                       reinterpret_cast<const uint32_t *>(tot + 1), tot + 2);
+    hipLaunchKernelGGL(gro_copy_kernel, dim3((uint32_t)(((uint64_t)n + 3) / 4)), dim3(SS_THREADS), 0,
+                       s, pkts, off, len, unit_log2, tot, gl, bG, rl, rfirst, ol, bO, seg, run,
+                       payload, cap, totals);
+    return hipGetLastError();
+}

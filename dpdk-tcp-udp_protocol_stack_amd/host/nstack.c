@@ -334,6 +334,17 @@ static int g_inplace;
  * fragment. */
 static uint32_t g_gro;
 static uint64_t g_gro_absorbed;
+/* Sequence ordering (nstack_set_rx_order): a burst's segments reach each
+ * connection in seq order (RXG_DLV_TCP_ORDER on the device paths,
+ * rxg_tcp_order_host in nstack_deliver).  g_order_moved (stat 16): records
+ * that changed position. */
+static int g_order;
+static uint64_t g_order_moved;
+/* the delivery flags the options ask for (g_lock held) */
+static uint32_t dlv_flags(void) {
+    return (g_inplace ? RXG_DLV_TCP_IN_PLACE : g_gro ? RXG_DLV_TCP_GRO : 0u) |
+           (g_order ? RXG_DLV_TCP_ORDER : 0u);
+}
 static void (*g_mb_release)(rxg_mbuf *m, void *arg);
 static void *g_mb_arg;
 static inline void mb_get(rxg_mbuf *m) { __atomic_fetch_add(&m->refcnt, 1, __ATOMIC_RELAXED); }
@@ -886,6 +897,7 @@ int nstack_init(int device, uint32_t max_burst, uint64_t max_bytes) {
             rxg_tune_deliver(g_ctx, RXG_DLV_TCP_GRO);
             rxg_tune_gro(g_ctx, g_gro);
         }
+        if (rc == RXG_OK && g_order) rxg_tune_deliver(g_ctx, dlv_flags());
         /* a new context: its delivery sets start again at set 0 */
         for (uint32_t j = 0; j < RXG_DELIVER_DEPTH; j++) g_set_ref[j] = -1;
         g_next_set = 0;
@@ -953,6 +965,8 @@ void nstack_fini(void) {
     g_inplace = 0; /* (options last one stack) */
     g_gro = 0;
     g_gro_absorbed = 0;
+    g_order = 0;
+    g_order_moved = 0;
     g_tx_encode = 0;
     atomic_store_explicit(&g_txe_frames, 0, memory_order_relaxed);
     g_tx_mss = 0;
@@ -1789,14 +1803,13 @@ int nstack_deliver(rxg_mbuf *const *m, uint32_t n, const rxg_verdict *v, uint64_
             if (!grow((void **)&s_handled, &s_handled_cap, n, 1) && sg) {
                 memset(s_handled, 0, n);
                 const uint32_t k = host_segments(m, n, v, sg);
-                /* coalescing: the runs by the rule's host restatement, the
-                 * source addresses read from the mbufs (out of memory: the
-                 * segments one by one) */
+                /* ordering and coalescing: the permutation and the runs by the
+                 * rules' host restatements, the source addresses read from the
+                 * mbufs (out of memory: arrival order, the segments one by one) */
                 rxg_tcp_run *run = NULL;
                 uint32_t nrun = 0;
-                uint32_t *sip = g_gro && k ? malloc((size_t)k * sizeof(*sip)) : NULL;
-                if (sip) run = malloc((size_t)k * sizeof(*run));
-                if (run) {
+                uint32_t *sip = (g_gro || g_order) && k ? malloc((size_t)k * sizeof(*sip)) : NULL;
+                if (sip)
                     for (uint32_t j = 0; j < k; j++) {
                         const rxg_mbuf *mb = m[sg[j].frame];
                         const uint8_t *f = (const uint8_t *)mb->buf_addr + mb->data_off;
@@ -1804,8 +1817,21 @@ int nstack_deliver(rxg_mbuf *const *m, uint32_t n, const rxg_verdict *v, uint64_
                         for (uint32_t q = 0; q < 4; q++)
                             if (26u + q < mb->data_len) sip[j] |= (uint32_t)f[26u + q] << (8u * q);
                     }
-                    if (rxg_tcp_runs_host(sg, sip, k, g_gro, run, &nrun) != RXG_OK) nrun = 0;
+                if (sip && g_order) {
+                    uint32_t *perm = malloc((size_t)k * sizeof(*perm)), moved = 0;
+                    rxg_segment *so = malloc((size_t)k * sizeof(*so));
+                    uint32_t *sipo = malloc((size_t)k * sizeof(*sipo));
+                    if (perm && so && sipo &&
+                        rxg_tcp_order_host(sg, sip, k, perm, &moved) == RXG_OK && moved) {
+                        for (uint32_t j = 0; j < k; j++) so[j] = sg[perm[j]], sipo[j] = sip[perm[j]];
+                        memcpy(sg, so, (size_t)k * sizeof(*sg));
+                        memcpy(sip, sipo, (size_t)k * sizeof(*sip));
+                        g_order_moved += moved;
+                    }
+                    free(perm), free(so), free(sipo);
                 }
+                if (sip && g_gro) run = malloc((size_t)k * sizeof(*run));
+                if (run && rxg_tcp_runs_host(sg, sip, k, g_gro, run, &nrun) != RXG_OK) nrun = 0;
                 deliver_tcp_sorted(sg, k, nrun ? run : NULL, nrun, NULL, -1, m, s_handled, rc_out);
                 free(sip), free(run);
                 done = s_handled;
@@ -2266,6 +2292,8 @@ static int deliver_part(rxg_mbuf *const *m, uint32_t k, const rxg_verdict *v, ui
     const rxg_tcp_run *run = NULL; /* (coalescing on at the submit: the burst's runs) */
     uint32_t nrun = 0;
     if (d->nseg && g_gro && rxg_delivery_runs(g_ctx, d, &run, &nrun) != RXG_OK) run = NULL, nrun = 0;
+    uint32_t moved = 0; /* (ordering on at the submit: the records that moved) */
+    if (d->nseg && g_order && rxg_delivery_moved(g_ctx, d, &moved) == RXG_OK) g_order_moved += moved;
     if (d->nseg)
         deliver_tcp_sorted(d->seg, d->nseg, nrun ? run : NULL, nrun, d->tcp_payload,
                            d->tcp_payload_ref, m, handled, rco);
@@ -2865,7 +2893,7 @@ int nstack_set_rx_gro(uint32_t W) {
     int rc = W && g_inplace ? RXG_EINVAL : RXG_OK; /* (payloads left in their frames) */
     if (rc == RXG_OK) {
         g_gro = W;
-        if (g_ctx && !g_inplace) rc = rxg_tune_deliver(g_ctx, W ? RXG_DLV_TCP_GRO : 0u);
+        if (g_ctx && !g_inplace) rc = rxg_tune_deliver(g_ctx, dlv_flags());
         if (g_ctx && W && rc == RXG_OK) rc = rxg_tune_gro(g_ctx, W);
     }
     pthread_mutex_unlock(&g_lock);
@@ -2881,10 +2909,15 @@ int nstack_set_rx_inplace(int on, void (*release)(rxg_mbuf *m, void *arg), void 
     g_inplace = on != 0;
     g_mb_release = release;
     g_mb_arg = arg;
-    const int rc = g_ctx ? rxg_tune_deliver(g_ctx, g_inplace ? RXG_DLV_TCP_IN_PLACE
-                                                   : g_gro   ? RXG_DLV_TCP_GRO
-                                                             : 0u)
-                         : RXG_OK;
+    const int rc = g_ctx ? rxg_tune_deliver(g_ctx, dlv_flags()) : RXG_OK;
+    pthread_mutex_unlock(&g_lock);
+    return rc;
+}
+
+int nstack_set_rx_order(int on) {
+    pthread_mutex_lock(&g_lock);
+    g_order = on != 0;
+    const int rc = g_ctx ? rxg_tune_deliver(g_ctx, dlv_flags()) : RXG_OK;
     pthread_mutex_unlock(&g_lock);
     return rc;
 }
@@ -3332,10 +3365,10 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
 }
 
 uint64_t nstack_stat(int which) {
-    if (which < 0 || which > 15) return 0;
-    if (which == 15) { /* segments absorbed by receive coalescing */
+    if (which < 0 || which > 16) return 0;
+    if (which >= 15) { /* segments absorbed by receive coalescing / moved by ordering */
         pthread_mutex_lock(&g_lock);
-        const uint64_t a = g_gro_absorbed;
+        const uint64_t a = which == 15 ? g_gro_absorbed : g_order_moved;
         pthread_mutex_unlock(&g_lock);
         return a;
     }

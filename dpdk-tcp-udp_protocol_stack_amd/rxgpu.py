@@ -111,7 +111,7 @@ assert SEGMENT_DTYPE.itemsize == 32
 TCP_RUN_DTYPE = np.dtype([("first", "<u4"), ("nseg", "<u4"), ("bytes", "<u4"), ("offset", "<u4")])
 assert TCP_RUN_DTYPE.itemsize == 16
 GRO_MAX_WINDOW, GRO_DEFAULT_WINDOW = 1 << 20, 65536
-DLV_TCP_IN_PLACE, DLV_TCP_GRO = 0x1, 0x2
+DLV_TCP_IN_PLACE, DLV_TCP_GRO, DLV_TCP_ORDER = 0x1, 0x2, 0x4
 # rxg_txd, the send descriptor of the TX encoder (K5): sip/dip/sport/dport/
 # window/urp raw as the reference stores them, seq/ack host order
 TXD_DTYPE = np.dtype([("dst_mac", "u1", (6,)), ("src_mac", "u1", (6,)), ("sip", "<u4"), ("dip", "<u4"),
@@ -183,6 +183,10 @@ _tcp_compact_dev = _sig("rxg_tcp_compact_dev", _i32, _vp, _vp, _vp, _vp, _u32, _
 _tcp_coalesce_dev = _sig("rxg_tcp_coalesce_dev", _i32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp,
                          _vp, _vp, _u64, _vp, _vp)
 _tcp_runs_host = _sig("rxg_tcp_runs_host", _i32, _vp, _vp, _u32, _u32, _vp, C.POINTER(_u32))
+_tcp_compact_ordered_dev = _sig("rxg_tcp_compact_ordered_dev", _i32, _vp, _vp, _vp, _vp, _u32, _u32,
+                                _vp, _u32, _vp, _vp, _vp, _u64, _vp, _vp)
+_tcp_order_host = _sig("rxg_tcp_order_host", _i32, _vp, _vp, _u32, _vp, C.POINTER(_u32))
+_delivery_moved = _sig("rxg_delivery_moved", _i32, _vp, _vp, C.POINTER(_u32))
 _tune_deliver = _sig("rxg_tune_deliver", _i32, _vp, _u32)
 _tune_gro = _sig("rxg_tune_gro", _i32, _vp, _u32)
 _delivery_runs = _sig("rxg_delivery_runs", _i32, _vp, _vp, C.POINTER(_vp), C.POINTER(_u32))
@@ -271,7 +275,8 @@ EXPORTED = ["rxg_open", "rxg_close", "rxg_strerror", "rxg_last_hip_error", "rxg_
             "rxg_flows_add", "rxg_flows_remove", "rxg_flows_update_udp", "rxg_flows_update_tcb",
             "rxg_flows_commit", "rxg_num_udp_ids", "rxg_flows_rebuilds", "rxg_udp_compact_dev",
             "rxg_process_mbufs_udp", "rxg_tcp_compact_dev", "rxg_tcp_coalesce_dev",
-            "rxg_tcp_runs_host", "rxg_tune_deliver", "rxg_tune_gro", "rxg_delivery_runs",
+            "rxg_tcp_runs_host", "rxg_tcp_compact_ordered_dev", "rxg_tcp_order_host",
+            "rxg_delivery_moved", "rxg_tune_deliver", "rxg_tune_gro", "rxg_delivery_runs",
             "rxg_process_mbufs_deliver",
             "rxg_deliver_submit", "rxg_deliver_wait", "rxg_tune_ingest",
             "rxg_register_host", "rxg_unregister_host", "rxg_payload_hold", "rxg_payload_release",
@@ -523,8 +528,30 @@ class Context:
                                  window, p(d_seg), p(d_run), p(d_payload), payload_cap,
                                  p(d_totals), stream), "rxg_tcp_coalesce_dev")
 
+    def tcp_compact_ordered_dev(self, d_pkts, d_off, d_len, n: int, off_unit_log2: int, d_v,
+                                window: int, d_seg, d_run, d_payload, payload_cap: int, d_totals,
+                                stream=None):
+        """K4 (window 0; d_payload None: records only) or its coalescing form on
+        the sequence-ordered segments (rxg_tcp_compact_ordered_dev), async on
+        stream; d_totals: 5 words, the last one the moved count"""
+        def p(x):
+            return x if (x is None or isinstance(x, int)) else x.data_ptr()
+        _check(_tcp_compact_ordered_dev(self._h, p(d_pkts), p(d_off), p(d_len), n, off_unit_log2,
+                                        p(d_v), window, p(d_seg), p(d_run), p(d_payload),
+                                        payload_cap, p(d_totals), stream),
+               "rxg_tcp_compact_ordered_dev")
+
+    def delivery_moved(self, handle) -> int:
+        """rxg_delivery_moved of a waited-for deliver_submit handle (0 with
+        DLV_TCP_ORDER off)"""
+        _, _, d = handle
+        mv = _u32()
+        _check(_delivery_moved(self._h, C.byref(d), C.byref(mv)), "rxg_delivery_moved")
+        return mv.value
+
     def tune_deliver(self, flags: int):
-        """rxg_tune_deliver: DLV_TCP_IN_PLACE or DLV_TCP_GRO (0 = the default)"""
+        """rxg_tune_deliver: DLV_TCP_IN_PLACE or DLV_TCP_GRO, either with
+        DLV_TCP_ORDER (0 = the default)"""
         _check(_tune_deliver(self._h, flags), "rxg_tune_deliver")
 
     def tune_gro(self, window: int):
@@ -805,6 +832,25 @@ def tcp_runs_host(seg: np.ndarray, sip: np.ndarray, window: int) -> np.ndarray:
     return run[:nrun.value].copy()
 
 
+def tcp_order_host(seg: np.ndarray, sip: np.ndarray):
+    """rxg_tcp_order_host: the sequence ordering of K4's records (seg,
+    SEGMENT_DTYPE) and their raw source addresses, on the CPU: (perm, moved),
+    perm[k] = the index of the record that takes position k"""
+    seg = np.ascontiguousarray(seg, SEGMENT_DTYPE)
+    sip = np.ascontiguousarray(sip, np.uint32)
+    assert len(seg) == len(sip)
+    if not len(seg): # (the call takes no NULL, and numpy's empty arrays may have one)
+        seg, sip = np.zeros(1, SEGMENT_DTYPE), np.zeros(1, np.uint32)
+        n = 0
+    else:
+        n = len(seg)
+    perm = np.zeros(max(n, 1), np.uint32)
+    moved = _u32()
+    _check(_tcp_order_host(seg.ctypes.data, sip.ctypes.data, n, perm.ctypes.data, C.byref(moved)),
+           "rxg_tcp_order_host")
+    return perm[:n].copy(), moved.value
+
+
 def tx_encode_tso_host(txd: np.ndarray, payload: np.ndarray, mss: int, cap_bytes: int, out_cap: int,
                        slot_bytes: int = 0, flags: int = 0, fill: int = 0, fill_entries: int = 0):
     """rxg_tx_encode_tso_host, the TX encoder with TCP segmentation on the CPU:
@@ -989,7 +1035,8 @@ class NStack:
                    ("nstack_tx_burst", _i32, [_vp, _u64, _vp, _vp, _u32, _i32, _vp]),
                    ("nstack_set_tx_encode", _i32, [_i32]),
                    ("nstack_set_tx_mss", _i32, [_u32]),
-                   ("nstack_set_rx_gro", _i32, [_u32])]
+                   ("nstack_set_rx_gro", _i32, [_u32]),
+                   ("nstack_set_rx_order", _i32, [_i32])]
             for name, res, args in sig:
                 f = getattr(lib, name)
                 f.restype, f.argtypes = res, args
@@ -1298,6 +1345,11 @@ class NStack:
         one receive fragment and one ACK per run of at most about `window` bytes
         (0 = off); raises RxgError (RXG_EINVAL) while in-place receive is on"""
         _check(self.lib.nstack_set_rx_gro(window), "nstack_set_rx_gro")
+
+    def set_rx_order(self, on: bool):
+        """nstack_set_rx_order: a burst's segments reach each connection in
+        sequence order (stat(16) counts the records moved)"""
+        _check(self.lib.nstack_set_rx_order(1 if on else 0), "nstack_set_rx_order")
 
     def tx_burst(self, max_frames: int = 256, cap_bytes: int = 1 << 20, cksum: bool = False):
         """one udp_out + tcp_out pass: the frames (bytes) it produced"""

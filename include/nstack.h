@@ -261,6 +261,22 @@ int nstack_set_rx_inplace(int on, void (*release)(rxg_mbuf *m, void *arg), void 
  * and nstack_set_rx_inplace(on) is RXG_EINVAL while W != 0.  nstack_stat(15)
  * counts the segments absorbed into a preceding segment's fragment. */
 int nstack_set_rx_gro(uint32_t W);
+/* TCP sequence ordering (the third piece beside nstack_set_tx_mss and
+ * nstack_set_rx_gro).  on == 0 (the default): a connection's segments of a
+ * burst reach its state machine in arrival order.  on != 0: in sequence order
+ * (the rule: rxgpu.h, "TCP sequence ordering"): the device paths
+ * (nstack_rx_burst, the halves, nstack_rx_submit / nstack_rx_complete) run
+ * the ordering form of the segment sort (RXG_DLV_TCP_ORDER), the host-verdict
+ * path (nstack_deliver) applies rxg_tcp_order_host to its records before the
+ * runs are computed.  Delivery itself follows record order as before.  Works
+ * with nstack_set_rx_gro (a train that arrived with a swapped pair coalesces
+ * as one run again) and with nstack_set_rx_inplace.  nstack_stat(16) adds up
+ * the records that changed position.  A burst delivered frame by frame
+ * because the lists changed under it (nstack_stat(5)) keeps arrival order.
+ * This reorders what a burst holds; it validates nothing: duplicates are not
+ * dropped, a hole is not waited for, and data of segments without PSH is not
+ * delivered.  TCP here is not loss-safe with it. */
+int nstack_set_rx_order(int on);
 /* Items the application has read (fragments, datagram batches) are handed
  * back to the protocol thread and freed by its next nstack_rx_burst (while
  * that burst is on the GPU) / nstack_tx_burst / nstack_deliver call (or
@@ -311,7 +327,8 @@ int nstack_set_halves(uint32_t min_half);
  * deliveries, read with acquire); 13 = frames produced by the TX encoder
  * (nstack_set_tx_encode); 14 = fragments sent as more than one frame in a
  * pass (nstack_set_tx_mss); 15 = segments absorbed into a preceding segment's
- * receive fragment (nstack_set_rx_gro).  Counter 1 also counts TX items dropped (a
+ * receive fragment (nstack_set_rx_gro); 16 = segment records moved by sequence
+ * ordering (nstack_set_rx_order).  Counter 1 also counts TX items dropped (a
  * send ring full, or a datagram too long for a frame). */
 uint64_t nstack_stat(int which);
 

@@ -443,6 +443,58 @@ int rxg_tcp_coalesce_dev(rxg_ctx *ctx, const uint8_t *d_pkts, const uint32_t *d_
 int rxg_tcp_runs_host(const rxg_segment *seg, const uint32_t *sip, uint32_t nseg, uint32_t W,
                       rxg_tcp_run *run, uint32_t *nrun);
 
+/* ---- TCP sequence ordering: the third piece beside TSO and GRO (opt-in)
+ * K4's sort is stable, so a connection's segments keep their arrival order,
+ * and the state machine never compares a segment's seq with rcv_nxt.  A burst
+ * whose segments arrived out of order (RSS split and gather, two bursts in
+ * flight, several NIC queues) therefore corrupts the byte stream.  The
+ * ordering form of K4 repairs the order inside the burst: a permutation stage
+ * between the sort and the record stage.  The rule, on the sorted records
+ * seg[0..nseg) in (flow, frame) order and each record's raw source address
+ * sip (frame bytes 26-29, 0 past the capture; rxg_tcp_runs_host's array):
+ *   movable(j): (flags & 0x06) == 0, neither SYN nor RST;
+ *   a group is a maximal range of consecutive movable records with equal
+ *   flow, sip, sport and dport; every other record is a group of one.  Groups
+ *   keep their positions and records move only inside their group: the SYNs
+ *   to a listener never move relative to each other (accept order and tcb
+ *   creation order are unchanged), and two sources that meet on the
+ *   listener's id are never mixed;
+ *   inside a group with first record h (in arrival order) let
+ *   d[j] = (int32_t)(seq[j] - seq[h]); the group's records are output in
+ *   ascending (d[j], j).  The cast is a bijection, so this is a total order
+ *   for any input; it is the wrap-aware sequence order whenever the group
+ *   spans less than 2^31 bytes.  Equal seq keeps arrival order: a pure ACK
+ *   stays before the data segment that follows it, a retransmitted duplicate
+ *   behind its original;
+ *   moved = the number of records whose position changed.
+ * A burst with no inversion comes out exactly as K4 or the coalescing form
+ * writes it, with moved = 0.
+ * This is reordering, not sequence validation: duplicates are not dropped,
+ * nothing stops at a hole, and data of segments without PSH is still not
+ * delivered (the reference's PSH-only rule).  Validation is a follow-up on the
+ * host; the option does NOT make TCP here loss-safe.
+ *
+ * One device call for both forms, asynchronous on `stream`.  W == 0:
+ * rxg_tcp_compact_dev's outputs (records and gather) in the new order; d_run
+ * may be NULL, and d_payload == NULL gives the records-only in-place form.
+ * W in 1 .. RXG_GRO_MAX_WINDOW: rxg_tcp_coalesce_dev's outputs on the new
+ * order (d_run and d_payload required).  d_totals (5 words) = {segments,
+ * payload bytes used, 1 if payload_cap was too small, runs (0 when W == 0),
+ * moved}.  Every other argument rule of the two calls holds.  The device
+ * workspace grows on demand (stream-ordered). */
+int rxg_tcp_compact_ordered_dev(rxg_ctx *ctx, const uint8_t *d_pkts, const uint32_t *d_off,
+                                const uint16_t *d_len, uint32_t n, uint32_t off_unit_log2,
+                                const rxg_verdict *d_v, uint32_t W, rxg_segment *d_seg,
+                                rxg_tcp_run *d_run, uint8_t *d_payload, uint64_t payload_cap,
+                                uint32_t *d_totals, void *stream);
+/* The same rule on records in host memory (no device, no context): perm[k]
+ * (room for nseg) = the index of the record that takes position k, *moved the
+ * count of k with perm[k] != k.  nseg == 0 is valid; a NULL argument is
+ * RXG_EINVAL.  The CPU path and the tests' second opinion; the device calls
+ * never fall back to it. */
+int rxg_tcp_order_host(const rxg_segment *seg, const uint32_t *sip, uint32_t nseg, uint32_t *perm,
+                       uint32_t *moved);
+
 /* One mbuf burst through the whole device half of delivery: classify
  * (rxg_process_mbufs), then the UDP compaction (when the UDP id space is at
  * most RXG_COMPACT_MAX_FLOWS; else dgram/first are NULL and ndgram 0) and
@@ -508,12 +560,22 @@ int rxg_deliver_wait(rxg_ctx *ctx, rxg_delivery *d, float ms[8]);
  * RXG_DLV_TCP_IN_PLACE (RXG_EINVAL): payloads that stay in their frames
  * cannot be made contiguous.  Off by default. */
 #define RXG_DLV_TCP_GRO 0x2u
+/* RXG_DLV_TCP_ORDER: the TCP half of a delivery burst runs the ordering form
+ * of K4 (rxg_tcp_compact_ordered_dev; the rule: "TCP sequence ordering"):
+ * alone, with RXG_DLV_TCP_GRO (W = the window of rxg_tune_gro) or with
+ * RXG_DLV_TCP_IN_PLACE (records only).  struct rxg_delivery is unchanged;
+ * rxg_delivery_moved reports the burst's count of moved records.  Off by
+ * default. */
+#define RXG_DLV_TCP_ORDER 0x4u
 int rxg_tune_deliver(rxg_ctx *ctx, uint32_t flags);
 int rxg_tune_gro(rxg_ctx *ctx, uint32_t W);
 /* The runs of a waited-for delivery burst: *run / *nrun, valid as long as the
  * burst's delivery set is; NULL / 0 when RXG_DLV_TCP_GRO was off for it. */
 int rxg_delivery_runs(rxg_ctx *ctx, const rxg_delivery *d, const rxg_tcp_run **run,
                       uint32_t *nrun);
+/* The moved count of a waited-for delivery burst; 0 when RXG_DLV_TCP_ORDER
+ * was off for it. */
+int rxg_delivery_moved(rxg_ctx *ctx, const rxg_delivery *d, uint32_t *moved);
 
 /* Keep a burst's TCP payload buffer (rxg_delivery.tcp_payload_ref) alive past
  * the context's next burst call — e.g. while receive fragments that point into
