@@ -78,6 +78,19 @@ hipError_t rx_order_launch(const uint8_t *pkts, const uint32_t *off, const uint1
                            uint32_t unit_log2, const uint4 *verd, uint32_t nt, uint32_t W,
                            rxg_segment *seg, rxg_tcp_run *run, uint8_t *payload, uint64_t cap,
                            uint32_t *totals, void *ws, hipStream_t s);
+bool rx_ddos_has_g(uint32_t g);
+uint32_t rx_ddos_auto_g(uint32_t len_hint);
+size_t rx_ddos_ws_bytes(uint32_t n, bool own_bits);
+hipError_t rx_ddos_bits_launch(const uint8_t *pkts, const uint32_t *off, const uint16_t *len,
+                               uint32_t n, uint32_t unit_log2, uint32_t g, uint32_t *bits,
+                               hipStream_t s);
+hipError_t rx_ddos_window_launch(const uint32_t *bits, const uint16_t *len, uint32_t n, double thresh,
+                                 rxg_ddos_state *st, uint8_t *flag, double *stat,
+                                 rxg_ddos_summary *sum, void *ws, hipStream_t s);
+hipError_t rx_ddos_launch(const uint8_t *pkts, const uint32_t *off, const uint16_t *len, uint32_t n,
+                          uint32_t unit_log2, uint32_t g, double thresh, rxg_ddos_state *st,
+                          uint32_t *bits, uint8_t *flag, double *stat, rxg_ddos_summary *sum, void *ws,
+                          hipStream_t s);
 size_t rx_compact_ws_bytes(uint32_t n, uint32_t nflows);
 hipError_t rx_compact_launch(const uint8_t *pkts, const uint32_t *off, const uint16_t *len,
                              uint32_t n, uint32_t unit_log2, const uint4 *verd, uint32_t nflows,
@@ -207,6 +220,15 @@ struct rxg_ctx {
     uint32_t tune_ingest = RXG_INGEST_AUTO; // rxg_tune_ingest
     uint32_t deliver_flags = 0;             // rxg_tune_deliver (RXG_DLV_*)
     uint32_t gro_window = RXG_GRO_DEFAULT_WINDOW; // rxg_tune_gro (RXG_DLV_TCP_GRO)
+    // the entropy flood detector (K6, rx_ddos.hip): rxg_tune_ddos /
+    // rxg_tune_ddos_thresh, the workspace of every detector call on this
+    // context, and the state and summary of the delivery bursts (RXG_DLV_DDOS)
+    uint32_t tune_ddos = 0;
+    double ddos_thresh = RXG_DDOS_DEFAULT_THRESH;
+    void *d_ddos_ws = nullptr;
+    size_t d_ddos_ws_cap = 0;
+    rxg_ddos_state *d_ddos_state = nullptr;
+    rxg_ddos_summary *d_ddos_sum = nullptr;
     rx_ft_dev ft{};
     uint32_t tune_g = 0, tune_p = 0, tune_fpg = 0, tune_pipe = ~0u; // rxg_tune override
     uint32_t tune_bpc = 0; // rxg_tune_grid: resident blocks per CU cap (0 = occupancy)
@@ -299,7 +321,8 @@ struct rxg_ctx {
     // device buffers are shared: every step runs on `stream`, in order) and its
     // phase events; a set's results stay valid until the set is reused
     struct delivery_set {
-        bool on = false, udp = false, tcp = false, gro = false, order = false;
+        bool on = false, udp = false, tcp = false, gro = false, order = false, ddos = false;
+        rxg_ddos_summary *h_ddos = nullptr; // (rxg_delivery_ddos)
         uint32_t nrun = 0;             // (rxg_delivery_runs)
         uint32_t moved = 0;            // (rxg_delivery_moved)
         rxg_tcp_run *h_ss_run = nullptr;
@@ -776,10 +799,13 @@ void rxg_close(rxg_ctx *c) {
     (void)hipFree(c->d_ss_run);
     (void)hipFree(c->d_ss_totals);
     (void)hipFree(c->d_ss_ws);
+    (void)hipFree(c->d_ddos_ws);
+    (void)hipFree(c->d_ddos_state);
+    (void)hipFree(c->d_ddos_sum);
     for (rxg_ctx::delivery_set &ds : c->dls) {
         for (void *h : {(void *)ds.h_cp_dg, (void *)ds.h_cp_first, (void *)ds.h_cp_totals,
                         (void *)ds.h_cp_payload, (void *)ds.h_ss_seg, (void *)ds.h_ss_payload,
-                        (void *)ds.h_ss_totals, (void *)ds.h_ss_run})
+                        (void *)ds.h_ss_totals, (void *)ds.h_ss_run, (void *)ds.h_ddos})
             if (h) (void)hipHostFree(h);
         for (hipEvent_t e : ds.tev)
             if (e) (void)hipEventDestroy(e);
@@ -1174,11 +1200,23 @@ int rxg_tune_tables(rxg_ctx *c, uint32_t flags) {
 }
 
 int rxg_tune_deliver(rxg_ctx *c, uint32_t flags) {
-    if (!c || (flags & ~(RXG_DLV_TCP_IN_PLACE | RXG_DLV_TCP_GRO | RXG_DLV_TCP_ORDER)))
+    if (!c || (flags & ~(RXG_DLV_TCP_IN_PLACE | RXG_DLV_TCP_GRO | RXG_DLV_TCP_ORDER | RXG_DLV_DDOS)))
         return RXG_EINVAL;
     // (payloads that stay in their frames cannot be made contiguous)
     if ((flags & RXG_DLV_TCP_IN_PLACE) && (flags & RXG_DLV_TCP_GRO)) return RXG_EINVAL;
     c->deliver_flags = flags;
+    return RXG_OK;
+}
+
+int rxg_tune_ddos(rxg_ctx *c, uint32_t lanes_per_frame) {
+    if (!c || (lanes_per_frame && !rx_ddos_has_g(lanes_per_frame))) return RXG_EINVAL;
+    c->tune_ddos = lanes_per_frame;
+    return RXG_OK;
+}
+
+int rxg_tune_ddos_thresh(rxg_ctx *c, double thresh) {
+    if (!c || thresh != thresh) return RXG_EINVAL;
+    c->ddos_thresh = thresh;
     return RXG_OK;
 }
 
@@ -1854,6 +1892,85 @@ int rxg_tcp_compact_ordered_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_
                       W, d_seg, d_run, d_payload, payload_cap, d_totals, (hipStream_t)stream);
 }
 
+// the detector's three launches on s; the context's workspace is grown first
+static int ddos_impl(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off, const uint16_t *d_len,
+                     uint32_t n, uint32_t off_unit_log2, uint32_t len_hint, double thresh,
+                     rxg_ddos_state *d_state, uint32_t *d_bits, uint8_t *d_flag, double *d_stat,
+                     rxg_ddos_summary *d_sum, hipStream_t s) {
+    const size_t ws = rx_ddos_ws_bytes(n, d_bits == nullptr);
+    if (ws > c->d_ddos_ws_cap) { // (its uses are ordered by the caller: freed and grown in stream order)
+        int rc = ensure_dev_async(&c->d_ddos_ws, &c->d_ddos_ws_cap, ws, s);
+        if (rc) return rc;
+    }
+    const uint32_t g = c->tune_ddos ? c->tune_ddos : rx_ddos_auto_g(len_hint);
+    HIPCHK(rx_ddos_launch(d_pkts, d_off, d_len, n, off_unit_log2, g, thresh, d_state, d_bits, d_flag,
+                          d_stat, d_sum, c->d_ddos_ws, s));
+    return RXG_OK;
+}
+
+int rxg_ddos_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off, const uint16_t *d_len,
+                 uint32_t n, uint32_t off_unit_log2, uint32_t len_hint, double thresh,
+                 rxg_ddos_state *d_state, uint32_t *d_bits, uint8_t *d_flag, double *d_stat,
+                 rxg_ddos_summary *d_summary, void *stream) {
+    if (!c) return RXG_EINVAL;
+    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
+    if (!d_state || !d_summary || (n && (!d_pkts || !d_off || !d_len))) return RXG_EINVAL;
+    if (thresh != thresh || off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
+    DEVGUARD(c);
+    return ddos_impl(c, d_pkts, d_off, d_len, n, off_unit_log2, len_hint, thresh, d_state, d_bits,
+                     d_flag, d_stat, d_summary, (hipStream_t)stream);
+}
+
+int rxg_ddos_bits_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off, const uint16_t *d_len,
+                      uint32_t n, uint32_t off_unit_log2, uint32_t len_hint, uint32_t *d_bits,
+                      void *stream) {
+    if (!c) return RXG_EINVAL;
+    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
+    if (n && (!d_pkts || !d_off || !d_len || !d_bits)) return RXG_EINVAL;
+    if (off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
+    DEVGUARD(c);
+    const uint32_t g = c->tune_ddos ? c->tune_ddos : rx_ddos_auto_g(len_hint);
+    HIPCHK(rx_ddos_bits_launch(d_pkts, d_off, d_len, n, off_unit_log2, g, d_bits, (hipStream_t)stream));
+    return RXG_OK;
+}
+
+int rxg_ddos_window_dev(rxg_ctx *c, const uint32_t *d_bits, const uint16_t *d_len, uint32_t n,
+                        double thresh, rxg_ddos_state *d_state, uint8_t *d_flag, double *d_stat,
+                        rxg_ddos_summary *d_summary, void *stream) {
+    if (!c) return RXG_EINVAL;
+    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
+    if (!d_state || !d_summary || (n && (!d_bits || !d_len)) || thresh != thresh) return RXG_EINVAL;
+    DEVGUARD(c);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t ws = rx_ddos_ws_bytes(n, false);
+    if (ws > c->d_ddos_ws_cap) {
+        int rc = ensure_dev_async(&c->d_ddos_ws, &c->d_ddos_ws_cap, ws, s);
+        if (rc) return rc;
+    }
+    HIPCHK(rx_ddos_window_launch(d_bits, d_len, n, thresh, d_state, d_flag, d_stat, d_summary,
+                                 c->d_ddos_ws, s));
+    return RXG_OK;
+}
+
+// (a delivery in flight is waited for first, like every other call on the context)
+int rxg_ddos_reset(rxg_ctx *c) {
+    if (!c) return RXG_EINVAL;
+    if (c->device == RXG_HOST_ONLY || !c->d_ddos_state) return RXG_OK; // (fresh at first use)
+    DEVGUARD(c);
+    HIPCHK(hipMemsetAsync(c->d_ddos_state, 0, sizeof(rxg_ddos_state), c->stream));
+    return RXG_OK;
+}
+
+int rxg_delivery_ddos(rxg_ctx *c, const rxg_delivery *d, rxg_ddos_summary *summary) {
+    if (!c || !d || !summary) return RXG_EINVAL;
+    memset(summary, 0, sizeof(*summary));
+    if (d->set < 1 || d->set > RXG_DELIVER_DEPTH) return RXG_EINVAL;
+    const rxg_ctx::delivery_set &ds = c->dls[d->set - 1];
+    if (ds.on) return RXG_EINVAL; // (not waited for yet)
+    if (ds.ddos) *summary = *ds.h_ddos;
+    return RXG_OK;
+}
+
 int rxg_delivery_moved(rxg_ctx *c, const rxg_delivery *d, uint32_t *moved) {
     if (!c || !d || !moved) return RXG_EINVAL;
     *moved = 0;
@@ -1926,6 +2043,15 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
         if (!ds.h_ss_run)
             HIPCHK(hipHostMalloc((void **)&ds.h_ss_run, (size_t)c->max_pkts * sizeof(rxg_tcp_run), 0));
     }
+    const bool ddos = (c->deliver_flags & RXG_DLV_DDOS) != 0;
+    if (ddos) {
+        if (!c->d_ddos_sum) HIPCHK(hipMalloc(&c->d_ddos_sum, sizeof(rxg_ddos_summary)));
+        if (!ds.h_ddos) HIPCHK(hipHostMalloc((void **)&ds.h_ddos, sizeof(rxg_ddos_summary), 0));
+        if (!c->d_ddos_state) { // fresh, ordered before the first burst's detector
+            HIPCHK(hipMalloc(&c->d_ddos_state, sizeof(rxg_ddos_state)));
+            HIPCHK(hipMemsetAsync(c->d_ddos_state, 0, sizeof(rxg_ddos_state), c->stream));
+        }
+    }
     for (hipEvent_t &e : ds.tev)
         if (!e) HIPCHK(hipEventCreate(&e));
     // the TCP payloads of this burst: a free pooled buffer (a hold the caller
@@ -1960,7 +2086,7 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
         d->udp_payload = ds.h_cp_payload;
         memset(ds.h_cp_first, 0, (nf + 1) * sizeof(uint32_t));
     }
-    ds.on = ds.udp = ds.tcp = ds.gro = ds.order = false;
+    ds.on = ds.udp = ds.tcp = ds.gro = ds.order = ds.ddos = false;
     ds.nrun = ds.moved = 0;
     ds.ticket = 0;
     ds.t0 = t0;
@@ -2006,6 +2132,17 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
                                    c->d_ss_totals, c->stream)))
                 return rc;
         }
+        // the flood detector (RXG_DLV_DDOS) reads the staged frames once more;
+        // bursts follow each other on the stream, so the window follows
+        // submit order.  Only its summary goes back.
+        if (ddos) {
+            if ((rc = ddos_impl(c, sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, (uint32_t)(st.span / n),
+                                c->ddos_thresh, c->d_ddos_state, nullptr, nullptr, nullptr,
+                                c->d_ddos_sum, c->stream)))
+                return rc;
+            HIPCHK(hipMemcpyAsync(ds.h_ddos, c->d_ddos_sum, sizeof(rxg_ddos_summary),
+                                  hipMemcpyDeviceToHost, c->stream));
+        }
         HIPCHK(hipEventRecord(ds.tev[3], c->stream)); // after K3 / K4
         // every result in one round trip: the counts with upper-bound copies of
         // the records (n of each) and payloads (the staged span bounds the sum of
@@ -2049,6 +2186,7 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
     ds.tcp = tcp;
     ds.gro = tcp && gro;
     ds.order = tcp && order;
+    ds.ddos = ddos;
     ds.ticket = t;
     ds.t1 = t1;
     return RXG_OK;

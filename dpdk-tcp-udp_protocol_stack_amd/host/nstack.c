@@ -340,10 +340,55 @@ static uint64_t g_gro_absorbed;
  * that changed position. */
 static int g_order;
 static uint64_t g_order_moved;
+/* The entropy flood detector (nstack_set_rx_ddos): every received frame goes
+ * through it in arrival order (RXG_DLV_DDOS on the device paths, rxg_ddos_host
+ * with g_ddos_state in nstack_deliver).  Detection only: nothing else reads
+ * what it finds.  g_ddos_acc: what nstack_ddos_status reports (alarm_frames
+ * is stat 17, rises stat 18). */
+static int g_ddos;
+static double g_ddos_thresh = RXG_DDOS_DEFAULT_THRESH;
+static rxg_ddos_state g_ddos_state;
+static nstack_ddos g_ddos_acc;
+/* one burst's summary into the running status (g_lock held); a burst the
+ * detector did not see has a zeroed summary */
+static void ddos_account(const rxg_ddos_summary *s) {
+    if (!s->frames_seen) return;
+    g_ddos_acc.frames_seen = s->frames_seen;
+    g_ddos_acc.alarm = s->flag;
+    g_ddos_acc.rises += s->rises;
+    g_ddos_acc.falls += s->falls;
+    g_ddos_acc.alarm_frames += s->alarm_frames;
+    g_ddos_acc.undef_frames += s->undef_frames;
+    g_ddos_acc.last_stat = s->last_stat;
+}
+/* the frames of a host-verdict burst through rxg_ddos_host (g_lock held):
+ * packed at 16-B aligned offsets first, since mbuf data lies anywhere (out of
+ * memory: the burst goes unseen) */
+static void ddos_host_burst(rxg_mbuf *const *m, uint32_t n) {
+    uint64_t bytes = 0;
+    for (uint32_t i = 0; i < n; i++) bytes += ((uint64_t)m[i]->data_len + 15u) & ~15ull;
+    uint8_t *pk = malloc(bytes ? bytes : 16);
+    uint32_t *off = malloc((size_t)n * sizeof(*off));
+    uint16_t *len = malloc((size_t)n * sizeof(*len));
+    if (pk && off && len && (bytes >> 4) <= 0xFFFFFFFFull) {
+        uint64_t pos = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            off[i] = (uint32_t)(pos >> 4);
+            len[i] = m[i]->data_len;
+            memcpy(pk + pos, (const uint8_t *)m[i]->buf_addr + m[i]->data_off, len[i]);
+            pos += ((uint64_t)len[i] + 15u) & ~15ull;
+        }
+        rxg_ddos_summary sum;
+        if (rxg_ddos_host(pk, off, len, n, 4, g_ddos_thresh, &g_ddos_state, NULL, NULL, NULL, &sum) ==
+            RXG_OK)
+            ddos_account(&sum);
+    }
+    free(pk), free(off), free(len);
+}
 /* the delivery flags the options ask for (g_lock held) */
 static uint32_t dlv_flags(void) {
     return (g_inplace ? RXG_DLV_TCP_IN_PLACE : g_gro ? RXG_DLV_TCP_GRO : 0u) |
-           (g_order ? RXG_DLV_TCP_ORDER : 0u);
+           (g_order ? RXG_DLV_TCP_ORDER : 0u) | (g_ddos ? RXG_DLV_DDOS : 0u);
 }
 static void (*g_mb_release)(rxg_mbuf *m, void *arg);
 static void *g_mb_arg;
@@ -898,6 +943,10 @@ int nstack_init(int device, uint32_t max_burst, uint64_t max_bytes) {
             rxg_tune_gro(g_ctx, g_gro);
         }
         if (rc == RXG_OK && g_order) rxg_tune_deliver(g_ctx, dlv_flags());
+        if (rc == RXG_OK && g_ddos) {
+            rxg_tune_deliver(g_ctx, dlv_flags());
+            rxg_tune_ddos_thresh(g_ctx, g_ddos_thresh);
+        }
         /* a new context: its delivery sets start again at set 0 */
         for (uint32_t j = 0; j < RXG_DELIVER_DEPTH; j++) g_set_ref[j] = -1;
         g_next_set = 0;
@@ -967,6 +1016,10 @@ void nstack_fini(void) {
     g_gro_absorbed = 0;
     g_order = 0;
     g_order_moved = 0;
+    g_ddos = 0;
+    g_ddos_thresh = RXG_DDOS_DEFAULT_THRESH;
+    memset(&g_ddos_state, 0, sizeof(g_ddos_state));
+    memset(&g_ddos_acc, 0, sizeof(g_ddos_acc));
     g_tx_encode = 0;
     atomic_store_explicit(&g_txe_frames, 0, memory_order_relaxed);
     g_tx_mss = 0;
@@ -1789,6 +1842,7 @@ int nstack_deliver(rxg_mbuf *const *m, uint32_t n, const rxg_verdict *v, uint64_
     if (rc == RXG_OK) {
         g_burst_stale = gen != g_snap_gen; /* classified against other lists */
         g_burst_mutated = 0;
+        if (g_ddos && n) ddos_host_burst(m, n); /* (sees the frames; changes nothing below) */
         const uint8_t *done = NULL;
         rxg_dgram *dg = NULL;
         uint32_t *first = NULL;
@@ -2294,6 +2348,8 @@ static int deliver_part(rxg_mbuf *const *m, uint32_t k, const rxg_verdict *v, ui
     if (d->nseg && g_gro && rxg_delivery_runs(g_ctx, d, &run, &nrun) != RXG_OK) run = NULL, nrun = 0;
     uint32_t moved = 0; /* (ordering on at the submit: the records that moved) */
     if (d->nseg && g_order && rxg_delivery_moved(g_ctx, d, &moved) == RXG_OK) g_order_moved += moved;
+    rxg_ddos_summary dsum; /* (the detector on at the submit: the burst's summary) */
+    if (g_ddos && rxg_delivery_ddos(g_ctx, d, &dsum) == RXG_OK) ddos_account(&dsum);
     if (d->nseg)
         deliver_tcp_sorted(d->seg, d->nseg, nrun ? run : NULL, nrun, d->tcp_payload,
                            d->tcp_payload_ref, m, handled, rco);
@@ -2922,6 +2978,25 @@ int nstack_set_rx_order(int on) {
     return rc;
 }
 
+int nstack_set_rx_ddos(int on, double thresh) {
+    if (thresh != thresh) return RXG_EINVAL;
+    pthread_mutex_lock(&g_lock);
+    g_ddos = on != 0;
+    g_ddos_thresh = thresh;
+    int rc = g_ctx ? rxg_tune_deliver(g_ctx, dlv_flags()) : RXG_OK;
+    if (g_ctx && rc == RXG_OK) rc = rxg_tune_ddos_thresh(g_ctx, thresh);
+    pthread_mutex_unlock(&g_lock);
+    return rc;
+}
+
+int nstack_ddos_status(nstack_ddos *out) {
+    if (!out) return RXG_EINVAL;
+    pthread_mutex_lock(&g_lock);
+    *out = g_ddos_acc;
+    pthread_mutex_unlock(&g_lock);
+    return RXG_OK;
+}
+
 void nstack_reclaim(void) { reclaim(); }
 
 void nstack_mbufs_put(rxg_mbuf *const *m, uint32_t n) {
@@ -3365,10 +3440,14 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
 }
 
 uint64_t nstack_stat(int which) {
-    if (which < 0 || which > 16) return 0;
-    if (which >= 15) { /* segments absorbed by receive coalescing / moved by ordering */
+    if (which < 0 || which > 18) return 0;
+    if (which >= 15) { /* segments absorbed by receive coalescing / moved by ordering; the
+                          flood detector's frames under alarm / rises */
         pthread_mutex_lock(&g_lock);
-        const uint64_t a = which == 15 ? g_gro_absorbed : g_order_moved;
+        const uint64_t a = which == 15   ? g_gro_absorbed
+                           : which == 16 ? g_order_moved
+                           : which == 17 ? g_ddos_acc.alarm_frames
+                                         : g_ddos_acc.rises;
         pthread_mutex_unlock(&g_lock);
         return a;
     }

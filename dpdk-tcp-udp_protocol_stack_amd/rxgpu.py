@@ -109,6 +109,22 @@ SEGMENT_DTYPE = np.dtype([("frame", "<u4"), ("flow", "<u4"), ("seq", "<u4"), ("a
 assert SEGMENT_DTYPE.itemsize == 32
 # rxg_tcp_run, a run of receive coalescing (rxg_tcp_coalesce_dev / rxg_tcp_runs_host)
 TCP_RUN_DTYPE = np.dtype([("first", "<u4"), ("nseg", "<u4"), ("bytes", "<u4"), ("offset", "<u4")])
+# the entropy flood detector (K6): rxg_ddos_state / rxg_ddos_summary and the
+# per-frame flag bits
+DDOS_WINDOW, DDOS_TILE, DDOS_DEFAULT_THRESH = 256, 256, 1200.0
+DDOS_WARMUP, DDOS_UNDEF, DDOS_ALARM, DDOS_RISE, DDOS_FALL = 0x01, 0x02, 0x04, 0x08, 0x10
+DDOS_LANES = (1, 8, 64)  # lanes per frame of the bits pass compiled in (tune_ddos; 0 = auto)
+DDOS_STATE_DTYPE = np.dtype([("frames_seen", "<u8"), ("flag", "<u4"), ("_r0", "<u4"),
+                             ("set", "<u4", (DDOS_WINDOW,)), ("tot", "<u4", (DDOS_WINDOW,))])
+assert DDOS_STATE_DTYPE.itemsize == 2064
+DDOS_SUMMARY_DTYPE = np.dtype([("frames_seen", "<u8"), ("last_stat", "<f8"), ("alarm_frames", "<u4"),
+                               ("first_alarm", "<u4"), ("rises", "<u4"), ("falls", "<u4"),
+                               ("undef_frames", "<u4"), ("flag", "<u4"), ("last_set", "<u4"),
+                               ("last_tot", "<u4")])
+assert DDOS_SUMMARY_DTYPE.itemsize == 48
+NSTACK_DDOS_DTYPE = np.dtype([("frames_seen", "<u8"), ("rises", "<u8"), ("falls", "<u8"),
+                              ("alarm_frames", "<u8"), ("undef_frames", "<u8"), ("last_stat", "<f8"),
+                              ("alarm", "<u4"), ("_r0", "<u4")])
 assert TCP_RUN_DTYPE.itemsize == 16
 GRO_MAX_WINDOW, GRO_DEFAULT_WINDOW = 1 << 20, 65536
 DLV_TCP_IN_PLACE, DLV_TCP_GRO, DLV_TCP_ORDER = 0x1, 0x2, 0x4
@@ -187,6 +203,18 @@ _tcp_compact_ordered_dev = _sig("rxg_tcp_compact_ordered_dev", _i32, _vp, _vp, _
                                 _vp, _u32, _vp, _vp, _vp, _u64, _vp, _vp)
 _tcp_order_host = _sig("rxg_tcp_order_host", _i32, _vp, _vp, _u32, _vp, C.POINTER(_u32))
 _delivery_moved = _sig("rxg_delivery_moved", _i32, _vp, _vp, C.POINTER(_u32))
+_f64 = C.c_double
+_ddos_dev = _sig("rxg_ddos_dev", _i32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _f64, _vp, _vp, _vp, _vp,
+                 _vp, _vp)
+_ddos_bits_dev = _sig("rxg_ddos_bits_dev", _i32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp)
+_ddos_window_dev = _sig("rxg_ddos_window_dev", _i32, _vp, _vp, _vp, _u32, _f64, _vp, _vp, _vp, _vp, _vp)
+_ddos_host = _sig("rxg_ddos_host", _i32, _vp, _vp, _vp, _u32, _u32, _f64, _vp, _vp, _vp, _vp, _vp)
+_ddos_entropy = _sig("rxg_ddos_entropy", _f64, _f64, _f64)
+_tune_ddos = _sig("rxg_tune_ddos", _i32, _vp, _u32)
+_tune_ddos_thresh = _sig("rxg_tune_ddos_thresh", _i32, _vp, _f64)
+_ddos_reset = _sig("rxg_ddos_reset", _i32, _vp)
+_delivery_ddos = _sig("rxg_delivery_ddos", _i32, _vp, _vp, _vp)
+DLV_DDOS = 0x10
 _tune_deliver = _sig("rxg_tune_deliver", _i32, _vp, _u32)
 _tune_gro = _sig("rxg_tune_gro", _i32, _vp, _u32)
 _delivery_runs = _sig("rxg_delivery_runs", _i32, _vp, _vp, C.POINTER(_vp), C.POINTER(_u32))
@@ -288,7 +316,10 @@ EXPORTED = ["rxg_open", "rxg_close", "rxg_strerror", "rxg_last_hip_error", "rxg_
             "rxg_tx_encode", "rxg_tx_encode_host", "rxg_tx_encode_tso_dev", "rxg_tx_encode_tso",
             "rxg_tx_encode_tso_host", "rxg_tx_tso_count", "rxg_tune_txe", "rxg_rss_split",
             "rxg_rss_split_dev", "rxg_gather_dev", "rxg_group_id", "rxg_group_open",
-            "rxg_group_close", "rxg_group_size", "rxg_counts_allreduce", "rxg_ctx_counts_allreduce"]
+            "rxg_group_close", "rxg_group_size", "rxg_counts_allreduce", "rxg_ctx_counts_allreduce",
+            "rxg_ddos_dev", "rxg_ddos_bits_dev", "rxg_ddos_window_dev", "rxg_ddos_host",
+            "rxg_ddos_entropy", "rxg_tune_ddos", "rxg_tune_ddos_thresh", "rxg_ddos_reset",
+            "rxg_delivery_ddos"]
 
 
 class RxgError(RuntimeError):
@@ -549,9 +580,57 @@ class Context:
         _check(_delivery_moved(self._h, C.byref(d), C.byref(mv)), "rxg_delivery_moved")
         return mv.value
 
+    def ddos_dev(self, d_pkts, d_off, d_len, n: int, off_unit_log2: int, len_hint: int,
+                 thresh: float, d_state, d_bits, d_flag, d_stat, d_summary, stream=None):
+        """rxg_ddos_dev: one burst through the entropy flood detector, async on
+        stream.  d_state (DDOS_STATE_DTYPE bytes) and d_summary
+        (DDOS_SUMMARY_DTYPE bytes) are device buffers; d_bits (u32), d_flag
+        (u8) and d_stat (f64) may each be None"""
+        def p(x):
+            return x if (x is None or isinstance(x, int)) else x.data_ptr()
+        _check(_ddos_dev(self._h, p(d_pkts), p(d_off), p(d_len), n, off_unit_log2, len_hint, thresh,
+                         p(d_state), p(d_bits), p(d_flag), p(d_stat), p(d_summary), stream),
+               "rxg_ddos_dev")
+
+    def ddos_bits_dev(self, d_pkts, d_off, d_len, n: int, off_unit_log2: int, len_hint: int, d_bits,
+                      stream=None):
+        """rxg_ddos_bits_dev: the detector's bits pass alone"""
+        def p(x):
+            return x if (x is None or isinstance(x, int)) else x.data_ptr()
+        _check(_ddos_bits_dev(self._h, p(d_pkts), p(d_off), p(d_len), n, off_unit_log2, len_hint,
+                              p(d_bits), stream), "rxg_ddos_bits_dev")
+
+    def ddos_window_dev(self, d_bits, d_len, n: int, thresh: float, d_state, d_flag, d_stat,
+                        d_summary, stream=None):
+        """rxg_ddos_window_dev: the window pass and state update on computed bits"""
+        def p(x):
+            return x if (x is None or isinstance(x, int)) else x.data_ptr()
+        _check(_ddos_window_dev(self._h, p(d_bits), p(d_len), n, thresh, p(d_state), p(d_flag),
+                                p(d_stat), p(d_summary), stream), "rxg_ddos_window_dev")
+
+    def tune_ddos(self, lanes_per_frame: int = 0, thresh: float | None = None):
+        """rxg_tune_ddos: lanes per frame of the bits pass (one of DDOS_LANES,
+        0 = auto); thresh, when given, is rxg_tune_ddos_thresh (DLV_DDOS)"""
+        _check(_tune_ddos(self._h, lanes_per_frame), "rxg_tune_ddos")
+        if thresh is not None:
+            _check(_tune_ddos_thresh(self._h, thresh), "rxg_tune_ddos_thresh")
+
+    def ddos_reset(self):
+        """rxg_ddos_reset: the context's own detector state (DLV_DDOS) made fresh"""
+        _check(_ddos_reset(self._h), "rxg_ddos_reset")
+
+    def delivery_ddos(self, handle=None) -> np.ndarray:
+        """rxg_delivery_ddos of a waited-for deliver_submit handle, or of the
+        last process_mbufs_deliver: the burst's summary (DDOS_SUMMARY_DTYPE
+        scalar; zeroed with DLV_DDOS off)"""
+        d = handle[2] if handle is not None else self._last_delivery
+        out = np.zeros(1, DDOS_SUMMARY_DTYPE)
+        _check(_delivery_ddos(self._h, C.byref(d), _ptr(out)), "rxg_delivery_ddos")
+        return out[0]
+
     def tune_deliver(self, flags: int):
         """rxg_tune_deliver: DLV_TCP_IN_PLACE or DLV_TCP_GRO, either with
-        DLV_TCP_ORDER (0 = the default)"""
+        DLV_TCP_ORDER, any of them with DLV_DDOS (0 = the default)"""
         _check(_tune_deliver(self._h, flags), "rxg_tune_deliver")
 
     def tune_gro(self, window: int):
@@ -588,6 +667,7 @@ class Context:
         ms = (C.c_float * 8)()
         _check(_process_mbufs_deliver(self._h, C.cast(arr, _vp), len(mbufs), _ptr(out),
                                       C.byref(d), ms), "rxg_process_mbufs_deliver")
+        self._last_delivery = d
         return self._delivery_results(out, d, ms)
 
     def _delivery_results(self, out, d, ms):
@@ -832,6 +912,35 @@ def tcp_runs_host(seg: np.ndarray, sip: np.ndarray, window: int) -> np.ndarray:
     return run[:nrun.value].copy()
 
 
+def ddos_entropy(set_bits: float, total_bits: float) -> float:
+    """rxg_ddos_entropy: e(s, t) as the reference writes it, in double"""
+    return _ddos_entropy(float(set_bits), float(total_bits))
+
+
+def ddos_host(pkts: np.ndarray, off: np.ndarray, lens: np.ndarray, off_unit_log2: int,
+              thresh: float = DDOS_DEFAULT_THRESH, state: np.ndarray | None = None,
+              want=("bits", "flag", "stat")):
+    """rxg_ddos_host: one burst through the entropy flood detector on the CPU.
+    state (DDOS_STATE_DTYPE, one element; fresh when None) is updated in
+    place.  Returns (bits, flag, stat, summary, state); an output not named
+    in `want` is passed as NULL and returned as None"""
+    n = len(lens)
+    if state is None:
+        state = np.zeros(1, DDOS_STATE_DTYPE)
+    assert state.dtype == DDOS_STATE_DTYPE and state.size == 1 and state.flags["C_CONTIGUOUS"]
+    pkts = np.ascontiguousarray(pkts, np.uint8)
+    off = np.ascontiguousarray(off, np.uint32)
+    lens = np.ascontiguousarray(lens, np.uint16)
+    bits = np.full(n, 0, np.uint32) if "bits" in want else None
+    flag = np.zeros(n, np.uint8) if "flag" in want else None
+    stat = np.zeros(n, np.float64) if "stat" in want else None
+    summ = np.zeros(1, DDOS_SUMMARY_DTYPE)
+    _check(_ddos_host(pkts.ctypes.data, off.ctypes.data, lens.ctypes.data, n, off_unit_log2, thresh,
+                      state.ctypes.data, _ptr(bits), _ptr(flag), _ptr(stat), summ.ctypes.data),
+           "rxg_ddos_host")
+    return bits, flag, stat, summ[0], state
+
+
 def tcp_order_host(seg: np.ndarray, sip: np.ndarray):
     """rxg_tcp_order_host: the sequence ordering of K4's records (seg,
     SEGMENT_DTYPE) and their raw source addresses, on the CPU: (perm, moved),
@@ -1036,7 +1145,9 @@ class NStack:
                    ("nstack_set_tx_encode", _i32, [_i32]),
                    ("nstack_set_tx_mss", _i32, [_u32]),
                    ("nstack_set_rx_gro", _i32, [_u32]),
-                   ("nstack_set_rx_order", _i32, [_i32])]
+                   ("nstack_set_rx_order", _i32, [_i32]),
+                   ("nstack_set_rx_ddos", _i32, [_i32, C.c_double]),
+                   ("nstack_ddos_status", _i32, [_vp])]
             for name, res, args in sig:
                 f = getattr(lib, name)
                 f.restype, f.argtypes = res, args
@@ -1350,6 +1461,18 @@ class NStack:
         """nstack_set_rx_order: a burst's segments reach each connection in
         sequence order (stat(16) counts the records moved)"""
         _check(self.lib.nstack_set_rx_order(1 if on else 0), "nstack_set_rx_order")
+
+    def set_rx_ddos(self, on: bool, thresh: float = DDOS_DEFAULT_THRESH):
+        """nstack_set_rx_ddos: every received frame through the entropy flood
+        detector (detection only; stat(17) frames under alarm, stat(18) rises)"""
+        _check(self.lib.nstack_set_rx_ddos(1 if on else 0, thresh), "nstack_set_rx_ddos")
+
+    def ddos_status(self) -> dict:
+        """nstack_ddos_status: frames_seen, rises, falls, alarm_frames,
+        undef_frames, last_stat, alarm"""
+        out = np.zeros(1, NSTACK_DDOS_DTYPE)
+        _check(self.lib.nstack_ddos_status(out.ctypes.data), "nstack_ddos_status")
+        return {k: out[0][k].item() for k in NSTACK_DDOS_DTYPE.names if not k.startswith("_")}
 
     def tx_burst(self, max_frames: int = 256, cap_bytes: int = 1 << 20, cksum: bool = False):
         """one udp_out + tcp_out pass: the frames (bytes) it produced"""

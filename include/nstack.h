@@ -277,6 +277,31 @@ int nstack_set_rx_gro(uint32_t W);
  * dropped, a hole is not waited for, and data of segments without PSH is not
  * delivered.  TCP here is not loss-safe with it. */
 int nstack_set_rx_order(int on);
+/* The reference's entropy flood detector over the received frames (the rule:
+ * rxgpu.h, "Entropy flood detector"; ddos_detect in the reference's I/O loop,
+ * before the burst goes into the protocol ring).  on == 0 (the default): off.
+ * on != 0: every frame of every burst goes through the detector in arrival
+ * order with threshold thresh (RXG_DDOS_DEFAULT_THRESH is the reference's;
+ * NaN is RXG_EINVAL): the device paths (nstack_rx_burst, the halves,
+ * nstack_rx_submit / nstack_rx_complete) set RXG_DLV_DDOS and the detector
+ * runs on the GPU against the context's state; the host-verdict path
+ * (nstack_deliver) runs rxg_ddos_host with a state of the stack's own.
+ * Detection only: every verdict, delivery and return code is what it is with
+ * the option off (the reference exits on a rising alarm; here the application
+ * reads nstack_ddos_status and decides).  nstack_stat(17) counts the frames
+ * received under alarm, nstack_stat(18) the rises.  nstack_fini resets the
+ * option, the state and the status. */
+typedef struct nstack_ddos {
+    uint64_t frames_seen;  /* frames the detector has seen (the last burst's state) */
+    uint64_t rises, falls; /* alarm edges */
+    uint64_t alarm_frames; /* frames checked with thresh < D */
+    uint64_t undef_frames; /* frames checked on an undefined window */
+    double last_stat;      /* D of the last frame seen (NaN: not checked, or undefined) */
+    uint32_t alarm;        /* the current alarm state */
+    uint32_t _r0;
+} nstack_ddos;
+int nstack_set_rx_ddos(int on, double thresh);
+int nstack_ddos_status(nstack_ddos *out);
 /* Items the application has read (fragments, datagram batches) are handed
  * back to the protocol thread and freed by its next nstack_rx_burst (while
  * that burst is on the GPU) / nstack_tx_burst / nstack_deliver call (or
@@ -328,7 +353,8 @@ int nstack_set_halves(uint32_t min_half);
  * (nstack_set_tx_encode); 14 = fragments sent as more than one frame in a
  * pass (nstack_set_tx_mss); 15 = segments absorbed into a preceding segment's
  * receive fragment (nstack_set_rx_gro); 16 = segment records moved by sequence
- * ordering (nstack_set_rx_order).  Counter 1 also counts TX items dropped (a
+ * ordering (nstack_set_rx_order); 17 = frames received under the flood detector's
+ * alarm, 18 = its rises (nstack_set_rx_ddos).  Counter 1 also counts TX items dropped (a
  * send ring full, or a datagram too long for a frame). */
 uint64_t nstack_stat(int which);
 

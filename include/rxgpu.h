@@ -589,6 +589,108 @@ int rxg_delivery_moved(rxg_ctx *ctx, const rxg_delivery *d, uint32_t *moved);
 int rxg_payload_hold(rxg_ctx *ctx, int32_t ref);
 int rxg_payload_release(rxg_ctx *ctx, int32_t ref);
 
+/* ---- Entropy flood detector (K6, csrc/rx_ddos.hip; opt-in)
+ * The reference passes every received frame through an entropy-based flood
+ * detector before the burst goes into the protocol ring (ddos_detect,
+ * .vscode/test.c:2846-2891, called at :2992-2997).  The rule, restated:
+ *   per frame j: set_j = the number of 1-bits in its len bytes, tot_j = 8 * len;
+ *   e(s, t) = (-s)*(log2 s - log2 t) - (t-s)*(log2(t-s) - log2 t) + log2 t,
+ *   in double, left to right as written (rxg_ddos_entropy);
+ *   the state is a ring of RXG_DDOS_WINDOW slots of (set, tot) and the alarm
+ *   flag; frame g (counted since the state was fresh) takes slot g mod 256;
+ *   frames g < 256 fill their slot and are not checked: the flag is untouched;
+ *   from g = 256 on, each frame writes its slot and is checked on the window
+ *   g-255 .. g:  S = sum set, T = sum tot (u32), E = sum e (double),
+ *   D = E - e(S, T), alarm = (thresh < D), and the flag becomes alarm.
+ * e is undefined for s == 0 or s >= t (the reference's NaN: 0 * -inf, the
+ * empty frame included).  A window that holds such a frame is undefined: D
+ * reads NaN, there is no alarm and the flag becomes 0, as the reference's NaN
+ * comparison does; "undefined" is decided from the integers.
+ * Divergences from the reference: the length is the frame's len, not the
+ * mbuf's buffer size (pkt->buf_len), and bytes past len never count (the
+ * reference's count_bit reads whole 8-byte words past the end); an alarm is
+ * only reported (the reference calls rte_exit on a rising alarm); thresh is a
+ * parameter (1200.0 in the reference).  This is the reference's statistic; no
+ * claim is made about its quality as a detector.
+ *
+ * rxg_ddos_state: zero-filled = fresh; the same layout on host and device. */
+#define RXG_DDOS_WINDOW 256u
+#define RXG_DDOS_TILE 256u /* frames per block of the device window pass */
+#define RXG_DDOS_DEFAULT_THRESH 1200.0
+typedef struct rxg_ddos_state {
+    uint64_t frames_seen;
+    uint32_t flag;  /* the current alarm state, 0 / 1 */
+    uint32_t _r0;   /* 0 */
+    uint32_t set[RXG_DDOS_WINDOW];
+    uint32_t tot[RXG_DDOS_WINDOW];
+} rxg_ddos_state;   /* 2064 bytes */
+/* per-frame flag bits */
+#define RXG_DDOS_WARMUP 0x01u /* g < 256: not checked */
+#define RXG_DDOS_UNDEF 0x02u  /* checked, the window is undefined */
+#define RXG_DDOS_ALARM 0x04u  /* checked, thresh < D */
+#define RXG_DDOS_RISE 0x08u   /* checked, the alarm rose on this frame */
+#define RXG_DDOS_FALL 0x10u   /* checked, the alarm fell on this frame */
+typedef struct rxg_ddos_summary {
+    uint64_t frames_seen;  /* after the burst */
+    double last_stat;      /* D of the burst's last frame; NaN: not checked, or undefined */
+    uint32_t alarm_frames; /* frames with RXG_DDOS_ALARM */
+    uint32_t first_alarm;  /* the first one's index in the burst, or 0xFFFFFFFF */
+    uint32_t rises, falls;
+    uint32_t undef_frames; /* frames with RXG_DDOS_UNDEF */
+    uint32_t flag;         /* the alarm state after the burst */
+    uint32_t last_set, last_tot; /* S, T of the burst's last frame (0 when not checked) */
+} rxg_ddos_summary;        /* 48 bytes */
+/* One burst through the detector on the device, asynchronous on `stream`.
+ * Frames as for rxg_classify_dev (d_off << off_unit_log2, off_unit_log2 >= 4).
+ * d_state is the caller's device buffer (several detectors can coexist);
+ * calls that share a state must be ordered by the caller, and so must calls
+ * on one context (they share its workspace, grown on demand in stream order).
+ * Per-frame outputs, each nullable: d_bits[j] = set_j, d_flag[j] = the
+ * RXG_DDOS_* bits, d_stat[j] = D, or NaN where the frame was not checked or
+ * its window is undefined.  d_summary is required and always written.  n == 0
+ * is valid and leaves the state as it is.  len_hint (typical frame length,
+ * 0 = unknown) picks the lanes per frame of the bits pass unless rxg_tune_ddos
+ * forces one.  RXG_EINVAL for a NaN thresh or off_unit_log2 < 4. */
+int rxg_ddos_dev(rxg_ctx *ctx, const uint8_t *d_pkts, const uint32_t *d_off, const uint16_t *d_len,
+                 uint32_t n, uint32_t off_unit_log2, uint32_t len_hint, double thresh,
+                 rxg_ddos_state *d_state, uint32_t *d_bits, uint8_t *d_flag, double *d_stat,
+                 rxg_ddos_summary *d_summary, void *stream);
+/* The two passes of rxg_ddos_dev apart (tools/ddos_sweep.py times them so):
+ * the bits pass alone (d_bits required), and the window pass with the state
+ * update on bits already computed.  Argument rules as above. */
+int rxg_ddos_bits_dev(rxg_ctx *ctx, const uint8_t *d_pkts, const uint32_t *d_off,
+                      const uint16_t *d_len, uint32_t n, uint32_t off_unit_log2, uint32_t len_hint,
+                      uint32_t *d_bits, void *stream);
+int rxg_ddos_window_dev(rxg_ctx *ctx, const uint32_t *d_bits, const uint16_t *d_len, uint32_t n,
+                        double thresh, rxg_ddos_state *d_state, uint8_t *d_flag, double *d_stat,
+                        rxg_ddos_summary *d_summary, void *stream);
+/* The CPU statement of the rule (no device, no context): a literal
+ * restatement that sums in slot order like the reference, with libm's log2.
+ * The same arguments on host memory; the tests' second opinion, and the
+ * detector of the host-verdict path.  The device calls never fall back to it. */
+int rxg_ddos_host(const uint8_t *pkts, const uint32_t *off, const uint16_t *len, uint32_t n,
+                  uint32_t off_unit_log2, double thresh, rxg_ddos_state *state, uint32_t *bits,
+                  uint8_t *flag, double *stat, rxg_ddos_summary *summary);
+/* e(s, t) as the reference writes it (ddos_entropy, test.c:2774-2780). */
+double rxg_ddos_entropy(double set_bits, double total_bits);
+/* Lanes per frame of the bits pass: 1, 8 or 64; 0 = chosen from len_hint.
+ * Anything not compiled in is RXG_EINVAL. */
+int rxg_tune_ddos(rxg_ctx *ctx, uint32_t lanes_per_frame);
+/* RXG_DLV_DDOS (rxg_tune_deliver, combinable with the three flags above): a
+ * delivery burst also runs the detector over its staged frames on the
+ * context's stream, against the context's own device state, with the
+ * threshold of rxg_tune_ddos_thresh (RXG_DDOS_DEFAULT_THRESH until set; NaN
+ * is RXG_EINVAL).  The window follows submit order, two bursts in flight
+ * included.  Detection only: verdicts, records and payloads are what they are
+ * without it, and only the summary crosses PCIe.  rxg_delivery_ddos returns
+ * the summary of a waited-for burst (zeroed when the flag was off for it);
+ * rxg_ddos_reset makes the context's state fresh.  struct rxg_delivery is
+ * unchanged.  Off by default. */
+#define RXG_DLV_DDOS 0x10u /* (0x8 is not a flag: rxg_tune_deliver keeps refusing it) */
+int rxg_tune_ddos_thresh(rxg_ctx *ctx, double thresh);
+int rxg_ddos_reset(rxg_ctx *ctx);
+int rxg_delivery_ddos(rxg_ctx *ctx, const rxg_delivery *d, rxg_ddos_summary *summary);
+
 /* TX checksum generation (the send side's per-frame work, udp.c:84-95 and
  * tcp.c:444-463): for every IPv4 frame of the burst, the IPv4 header checksum
  * (rte_ipv4_cksum, rte_ip.h:255-265) is written at frame offset 24, and for
