@@ -91,6 +91,11 @@ hipError_t rx_ddos_launch(const uint8_t *pkts, const uint32_t *off, const uint16
                           uint32_t unit_log2, uint32_t g, double thresh, rxg_ddos_state *st,
                           uint32_t *bits, uint8_t *flag, double *stat, rxg_ddos_summary *sum, void *ws,
                           hipStream_t s);
+size_t rx_assemble_ws_bytes(uint32_t n);
+hipError_t rx_assemble_launch(const uint8_t *pkts, const uint32_t *off, const uint16_t *len,
+                              uint32_t n, uint32_t unit_log2, const uint4 *verd, uint32_t nt,
+                              rxg_segment *seg, rxg_tcp_stream *stream, uint8_t *payload,
+                              uint64_t cap, uint32_t *totals, void *ws, hipStream_t s);
 size_t rx_compact_ws_bytes(uint32_t n, uint32_t nflows);
 hipError_t rx_compact_launch(const uint8_t *pkts, const uint32_t *off, const uint16_t *len,
                              uint32_t n, uint32_t unit_log2, const uint4 *verd, uint32_t nflows,
@@ -308,6 +313,7 @@ struct rxg_ctx {
     rxg_segment *d_ss_seg = nullptr;
     uint8_t *d_ss_payload = nullptr;
     rxg_tcp_run *d_ss_run = nullptr; // (RXG_DLV_TCP_GRO: first use)
+    rxg_tcp_stream *d_ss_stream = nullptr; // (RXG_DLV_TCP_ASSEMBLE: first use)
     // pinned payload buffers a caller may keep past the next burst
     // (rxg_payload_hold / _release: the receive fragments of a burst point
     // into them until the application has read them); refs counts the holds,
@@ -322,6 +328,9 @@ struct rxg_ctx {
     // phase events; a set's results stay valid until the set is reused
     struct delivery_set {
         bool on = false, udp = false, tcp = false, gro = false, order = false, ddos = false;
+        bool assemble = false;
+        uint32_t nstream = 0;          // (rxg_delivery_streams)
+        rxg_tcp_stream *h_ss_stream = nullptr;
         rxg_ddos_summary *h_ddos = nullptr; // (rxg_delivery_ddos)
         uint32_t nrun = 0;             // (rxg_delivery_runs)
         uint32_t moved = 0;            // (rxg_delivery_moved)
@@ -797,6 +806,7 @@ void rxg_close(rxg_ctx *c) {
     (void)hipFree(c->d_ss_seg);
     (void)hipFree(c->d_ss_payload);
     (void)hipFree(c->d_ss_run);
+    (void)hipFree(c->d_ss_stream);
     (void)hipFree(c->d_ss_totals);
     (void)hipFree(c->d_ss_ws);
     (void)hipFree(c->d_ddos_ws);
@@ -805,7 +815,8 @@ void rxg_close(rxg_ctx *c) {
     for (rxg_ctx::delivery_set &ds : c->dls) {
         for (void *h : {(void *)ds.h_cp_dg, (void *)ds.h_cp_first, (void *)ds.h_cp_totals,
                         (void *)ds.h_cp_payload, (void *)ds.h_ss_seg, (void *)ds.h_ss_payload,
-                        (void *)ds.h_ss_totals, (void *)ds.h_ss_run, (void *)ds.h_ddos})
+                        (void *)ds.h_ss_totals, (void *)ds.h_ss_run, (void *)ds.h_ss_stream,
+                        (void *)ds.h_ddos})
             if (h) (void)hipHostFree(h);
         for (hipEvent_t e : ds.tev)
             if (e) (void)hipEventDestroy(e);
@@ -1200,10 +1211,14 @@ int rxg_tune_tables(rxg_ctx *c, uint32_t flags) {
 }
 
 int rxg_tune_deliver(rxg_ctx *c, uint32_t flags) {
-    if (!c || (flags & ~(RXG_DLV_TCP_IN_PLACE | RXG_DLV_TCP_GRO | RXG_DLV_TCP_ORDER | RXG_DLV_DDOS)))
+    if (!c || (flags & ~(RXG_DLV_TCP_IN_PLACE | RXG_DLV_TCP_GRO | RXG_DLV_TCP_ORDER | RXG_DLV_DDOS |
+                         RXG_DLV_TCP_ASSEMBLE)))
         return RXG_EINVAL;
     // (payloads that stay in their frames cannot be made contiguous)
     if ((flags & RXG_DLV_TCP_IN_PLACE) && (flags & RXG_DLV_TCP_GRO)) return RXG_EINVAL;
+    // (the streams are the coalesced form already, and they are gathered)
+    if ((flags & RXG_DLV_TCP_ASSEMBLE) && (flags & (RXG_DLV_TCP_IN_PLACE | RXG_DLV_TCP_GRO)))
+        return RXG_EINVAL;
     c->deliver_flags = flags;
     return RXG_OK;
 }
@@ -1835,6 +1850,22 @@ static int order_impl(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off, 
     return RXG_OK;
 }
 
+// the sort, the ordering stage and the stream assembly (rx_segsort.hip); the
+// workspace is K4's, grown
+static int assemble_impl(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off,
+                         const uint16_t *d_len, uint32_t n, uint32_t off_unit_log2, const uint4 *d_v,
+                         rxg_segment *d_seg, rxg_tcp_stream *d_stream, uint8_t *d_payload,
+                         uint64_t cap, uint32_t *d_totals, hipStream_t s) {
+    const size_t ws = rx_assemble_ws_bytes(n);
+    if (ws > c->d_ss_ws_cap) {
+        int rc = ensure_dev_async(&c->d_ss_ws, &c->d_ss_ws_cap, ws, s);
+        if (rc) return rc;
+    }
+    HIPCHK(rx_assemble_launch(d_pkts, d_off, d_len, n, off_unit_log2, d_v, c->fs.tcp.id_space(), d_seg,
+                              d_stream, d_payload, cap, d_totals, c->d_ss_ws, s));
+    return RXG_OK;
+}
+
 int rxg_payload_hold(rxg_ctx *c, int32_t ref) {
     if (!c || ref < 0 || ref >= RXG_PAYLOAD_BUFS) return RXG_EINVAL;
     c->pl[ref].refs.fetch_add(1, std::memory_order_acq_rel);
@@ -1971,6 +2002,33 @@ int rxg_delivery_ddos(rxg_ctx *c, const rxg_delivery *d, rxg_ddos_summary *summa
     return RXG_OK;
 }
 
+int rxg_tcp_assemble_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off,
+                         const uint16_t *d_len, uint32_t n, uint32_t off_unit_log2,
+                         const rxg_verdict *d_v, rxg_segment *d_seg, rxg_tcp_stream *d_stream,
+                         uint8_t *d_payload, uint64_t payload_cap, uint32_t *d_totals, void *stream) {
+    if (!c) return RXG_EINVAL;
+    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
+    if (!d_totals || !d_payload) return RXG_EINVAL;
+    if (n && (!d_pkts || !d_off || !d_len || !d_v || !d_seg || !d_stream)) return RXG_EINVAL;
+    if (off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
+    DEVGUARD(c);
+    return assemble_impl(c, d_pkts, d_off, d_len, n, off_unit_log2,
+                         reinterpret_cast<const uint4 *>(d_v), d_seg, d_stream, d_payload,
+                         payload_cap, d_totals, (hipStream_t)stream);
+}
+
+int rxg_delivery_streams(rxg_ctx *c, const rxg_delivery *d, const rxg_tcp_stream **stream,
+                         uint32_t *nstream) {
+    if (!c || !d || !stream || !nstream) return RXG_EINVAL;
+    *stream = nullptr;
+    *nstream = 0;
+    if (d->set < 1 || d->set > RXG_DELIVER_DEPTH) return RXG_EINVAL;
+    const rxg_ctx::delivery_set &ds = c->dls[d->set - 1];
+    if (ds.on) return RXG_EINVAL; // (not waited for yet)
+    if (ds.assemble && ds.nstream) *stream = ds.h_ss_stream, *nstream = ds.nstream;
+    return RXG_OK;
+}
+
 int rxg_delivery_moved(rxg_ctx *c, const rxg_delivery *d, uint32_t *moved) {
     if (!c || !d || !moved) return RXG_EINVAL;
     *moved = 0;
@@ -2031,13 +2089,22 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
     if (!ds.h_ss_totals) {
         if (!c->d_ss_seg) HIPCHK(hipMalloc(&c->d_ss_seg, (size_t)c->max_pkts * sizeof(rxg_segment)));
         if (!c->d_ss_payload) HIPCHK(hipMalloc(&c->d_ss_payload, c->max_bytes));
-        if (!c->d_ss_totals) HIPCHK(hipMalloc(&c->d_ss_totals, 5 * sizeof(uint32_t)));
+        if (!c->d_ss_totals) HIPCHK(hipMalloc(&c->d_ss_totals, 6 * sizeof(uint32_t)));
         if (!ds.h_ss_seg)
             HIPCHK(hipHostMalloc((void **)&ds.h_ss_seg, (size_t)c->max_pkts * sizeof(rxg_segment), 0));
-        HIPCHK(hipHostMalloc((void **)&ds.h_ss_totals, 5 * sizeof(uint32_t), 0));
+        HIPCHK(hipHostMalloc((void **)&ds.h_ss_totals, 6 * sizeof(uint32_t), 0));
     }
     const bool gro = (c->deliver_flags & RXG_DLV_TCP_GRO) != 0;
-    const bool order = (c->deliver_flags & RXG_DLV_TCP_ORDER) != 0;
+    const bool assemble = (c->deliver_flags & RXG_DLV_TCP_ASSEMBLE) != 0;
+    // (assembly runs the ordering stage itself and reports its moved count)
+    const bool order = (c->deliver_flags & RXG_DLV_TCP_ORDER) != 0 || assemble;
+    if (assemble) {
+        if (!c->d_ss_stream)
+            HIPCHK(hipMalloc(&c->d_ss_stream, (size_t)c->max_pkts * sizeof(rxg_tcp_stream)));
+        if (!ds.h_ss_stream)
+            HIPCHK(hipHostMalloc((void **)&ds.h_ss_stream,
+                                 (size_t)c->max_pkts * sizeof(rxg_tcp_stream), 0));
+    }
     if (gro) {
         if (!c->d_ss_run) HIPCHK(hipMalloc(&c->d_ss_run, (size_t)c->max_pkts * sizeof(rxg_tcp_run)));
         if (!ds.h_ss_run)
@@ -2086,8 +2153,8 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
         d->udp_payload = ds.h_cp_payload;
         memset(ds.h_cp_first, 0, (nf + 1) * sizeof(uint32_t));
     }
-    ds.on = ds.udp = ds.tcp = ds.gro = ds.order = ds.ddos = false;
-    ds.nrun = ds.moved = 0;
+    ds.on = ds.udp = ds.tcp = ds.gro = ds.order = ds.ddos = ds.assemble = false;
+    ds.nrun = ds.moved = ds.nstream = 0;
     ds.ticket = 0;
     ds.t0 = t0;
     c->dl_next = (si + 1) % RXG_DELIVER_DEPTH;
@@ -2115,7 +2182,12 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
                                    c->stream)))
                 return rc;
         tcp = c->fs.tcp.id_space() > 0;
-        if (tcp && order) {
+        if (tcp && assemble) {
+            if ((rc = assemble_impl(c, sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, sl.d_out, c->d_ss_seg,
+                                    c->d_ss_stream, c->d_ss_payload, c->max_bytes, c->d_ss_totals,
+                                    c->stream)))
+                return rc;
+        } else if (tcp && order) {
             if ((rc = order_impl(c, sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, sl.d_out,
                                  gro ? c->gro_window : 0u, c->d_ss_seg, c->d_ss_run,
                                  inplace ? nullptr : c->d_ss_payload, c->max_bytes, c->d_ss_totals,
@@ -2161,8 +2233,12 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
         }
         if (tcp) {
             HIPCHK(hipMemcpyAsync(ds.h_ss_totals, c->d_ss_totals,
-                                  (order ? 5 : gro ? 4 : 3) * sizeof(uint32_t),
+                                  (assemble ? 6 : order ? 5 : gro ? 4 : 3) * sizeof(uint32_t),
                                   hipMemcpyDeviceToHost, c->stream));
+            if (assemble) // (the streams cross with the records: at most n of them)
+                HIPCHK(hipMemcpyAsync(ds.h_ss_stream, c->d_ss_stream,
+                                      (size_t)n * sizeof(rxg_tcp_stream), hipMemcpyDeviceToHost,
+                                      c->stream));
             if (gro) // (the runs cross with the records: at most n of them)
                 HIPCHK(hipMemcpyAsync(ds.h_ss_run, c->d_ss_run, (size_t)n * sizeof(rxg_tcp_run),
                                       hipMemcpyDeviceToHost, c->stream));
@@ -2186,6 +2262,7 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
     ds.tcp = tcp;
     ds.gro = tcp && gro;
     ds.order = tcp && order;
+    ds.assemble = tcp && assemble;
     ds.ddos = ddos;
     ds.ticket = t;
     ds.t1 = t1;
@@ -2213,6 +2290,7 @@ int rxg_deliver_wait(rxg_ctx *c, rxg_delivery *d, float ms[8]) {
     if (tcp) d->nseg = ds.h_ss_totals[0], d->tcp_bytes = ds.h_ss_totals[1];
     if (ds.gro) ds.nrun = ds.h_ss_totals[3];
     if (ds.order) ds.moved = ds.h_ss_totals[4];
+    if (ds.assemble) ds.nstream = ds.h_ss_totals[3];
     if (ms) {
         ms[0] = (float)(ds.t1 - ds.t0);
         for (int k = 0; k < 4; ++k) HIPCHK(hipEventElapsedTime(&ms[k + 1], ds.tev[k], ds.tev[k + 1]));

@@ -340,6 +340,22 @@ static uint64_t g_gro_absorbed;
  * that changed position. */
 static int g_order;
 static uint64_t g_order_moved;
+/* Stream assembly (nstack_set_rx_assemble): a connection's segments of a burst
+ * are ordered, then assembled into contiguous byte ranges with duplicates
+ * dropped, overlaps trimmed and a stop at every hole (RXG_DLV_TCP_ASSEMBLE on
+ * the device paths; rxg_tcp_order_host, then rxg_tcp_assemble_host in
+ * nstack_deliver), and every stream is aligned with rcv_nxt before anything is
+ * queued (the host rule: rxgpu.h, "TCP stream assembly").  g_asm_dup (stat
+ * 19): payload bytes discarded as already received; g_asm_hole (stat 20):
+ * streams ignored behind a hole. */
+static int g_assemble;
+static uint64_t g_asm_dup, g_asm_hole;
+/* a burst's streams as deliver_tcp_sorted takes them (NULL: assembly off);
+ * the records then carry ncopy = take */
+struct asm_view {
+    const rxg_tcp_stream *st;
+    uint32_t n;
+};
 /* The entropy flood detector (nstack_set_rx_ddos): every received frame goes
  * through it in arrival order (RXG_DLV_DDOS on the device paths, rxg_ddos_host
  * with g_ddos_state in nstack_deliver).  Detection only: nothing else reads
@@ -388,7 +404,8 @@ static void ddos_host_burst(rxg_mbuf *const *m, uint32_t n) {
 /* the delivery flags the options ask for (g_lock held) */
 static uint32_t dlv_flags(void) {
     return (g_inplace ? RXG_DLV_TCP_IN_PLACE : g_gro ? RXG_DLV_TCP_GRO : 0u) |
-           (g_order ? RXG_DLV_TCP_ORDER : 0u) | (g_ddos ? RXG_DLV_DDOS : 0u);
+           (g_order ? RXG_DLV_TCP_ORDER : 0u) | (g_ddos ? RXG_DLV_DDOS : 0u) |
+           (g_assemble ? RXG_DLV_TCP_ASSEMBLE : 0u);
 }
 static void (*g_mb_release)(rxg_mbuf *m, void *arg);
 static void *g_mb_arg;
@@ -942,7 +959,7 @@ int nstack_init(int device, uint32_t max_burst, uint64_t max_bytes) {
             rxg_tune_deliver(g_ctx, RXG_DLV_TCP_GRO);
             rxg_tune_gro(g_ctx, g_gro);
         }
-        if (rc == RXG_OK && g_order) rxg_tune_deliver(g_ctx, dlv_flags());
+        if (rc == RXG_OK && (g_order || g_assemble)) rxg_tune_deliver(g_ctx, dlv_flags());
         if (rc == RXG_OK && g_ddos) {
             rxg_tune_deliver(g_ctx, dlv_flags());
             rxg_tune_ddos_thresh(g_ctx, g_ddos_thresh);
@@ -1016,6 +1033,8 @@ void nstack_fini(void) {
     g_gro_absorbed = 0;
     g_order = 0;
     g_order_moved = 0;
+    g_assemble = 0;
+    g_asm_dup = g_asm_hole = 0;
     g_ddos = 0;
     g_ddos_thresh = RXG_DDOS_DEFAULT_THRESH;
     memset(&g_ddos_state, 0, sizeof(g_ddos_state));
@@ -1568,6 +1587,65 @@ static void tcp_enqueue_rcv(struct tcp_stream *s, const uint8_t *f, uint32_t cap
     }
 }
 
+/* Stream assembly on, one frame of an ESTABLISHED connection on the
+ * frame-by-frame path: the host rule of rxgpu.h ("TCP stream assembly") on a
+ * stream of one (seq, bytes = the payload when it was captured whole, with or
+ * without PSH; FIN when the frame was usable).  Bytes below rcv_nxt are passed
+ * over, a frame behind a hole only draws an ACK. */
+static void tcp_dispatch_assembled(struct tcp_stream *s, const uint8_t *f, uint32_t cap, int tcplen,
+                                   uint8_t fl, uint16_t sport, uint16_t dport, uint32_t seq,
+                                   uint32_t ack) {
+    if (fl & 0x06u) return; /* (SYN or RST: left alone, no bytes, no FIN) */
+    const uint32_t hl = (cap > 46 ? f[46] : 0) >> 4;
+    const int plen = tcplen - (int)hl * 4;
+    const uint32_t from = 34 + hl * 4, avail = cap > from ? cap - from : 0;
+    const int usable = plen <= 0 || avail >= (uint32_t)plen;
+    const uint32_t bytes = plen > 0 && usable ? (uint32_t)plen : 0;
+    const int fin = (fl & TCP_FIN) && usable;
+    if (!bytes && !fin) return; /* (a pure ACK) */
+    const int32_t d = (int32_t)(s->rcv_nxt - seq);
+    if (d < 0) { /* behind a hole */
+        g_asm_hole++;
+        queue_ctl(s, dport, sport, TCP_ACK);
+        return;
+    }
+    const uint32_t fresh = bytes > (uint32_t)d ? bytes - (uint32_t)d : 0;
+    g_asm_dup += bytes - fresh;
+    if (fresh) {
+        struct tcp_fragment *fr = calloc(1, sizeof(*fr));
+        if (fr) fr->data = malloc((size_t)fresh + 1);
+        if (fr && fr->data) {
+            fr->dport = ntohs(dport);
+            fr->sport = ntohs(sport);
+            memcpy(fr->data, f + from + (uint32_t)d, fresh);
+            fr->data[fresh] = 0;
+            fr->length = fresh;
+            pthread_mutex_lock(&s->mutex);
+            int e = tq_push(s->rcvbuf, &s->rq, fr);
+            if (!e) pthread_cond_signal(&s->cond);
+            pthread_mutex_unlock(&s->mutex);
+            if (e) {
+                free(fr->data);
+                free(fr);
+                g_stat[1]++;
+            } else {
+                g_stat[4]++;
+            }
+        } else {
+            free(fr);
+        }
+        s->rcv_nxt += fresh;
+    }
+    if (fin && (uint32_t)d <= bytes) {
+        s->status = TCP_STATUS_CLOSE_WAIT;
+        restate_tcb(s, 0);
+        tcp_enqueue_rcv(s, f, cap, (int)hl * 4); /* EOF marker (payloadlen 0) */
+        s->rcv_nxt += 1;
+    }
+    s->snd_nxt = ack;
+    queue_ctl(s, dport, sport, TCP_ACK);
+}
+
 /* tcp_process after the lookup (tcp.c:373-415) for the frame's tcb (g_lock held) */
 static void tcp_dispatch(struct tcp_stream *s, const uint8_t *f, uint32_t cap) {
     const uint8_t fl = cap > 47 ? f[47] : 0;
@@ -1603,6 +1681,10 @@ static void tcp_dispatch(struct tcp_stream *s, const uint8_t *f, uint32_t cap) {
         break;
     case TCP_STATUS_ESTABLISHED: { /* tcp_handle_established, tcp.c:218-297 */
         const int tcplen = (int)(cap >= 18 ? ((uint32_t)f[16] << 8 | f[17]) : 0) - 20; /* :391 */
+        if (g_assemble) { /* the frame as a stream of one, aligned with rcv_nxt */
+            tcp_dispatch_assembled(s, f, cap, tcplen, fl, sport, dport, seq, ack);
+            break;
+        }
         if (fl & TCP_PSH) {
             tcp_enqueue_rcv(s, f, cap, tcplen);
             const int plen = tcplen - (int)((cap > 46 ? f[46] : 0) >> 4) * 4;
@@ -1763,8 +1845,8 @@ static int deliver_burst(rxg_mbuf *const *m, uint32_t n, const rxg_verdict *v, i
 }
 
 static void deliver_tcp_sorted(const rxg_segment *sg, uint32_t nseg, const rxg_tcp_run *run,
-                               uint32_t nrun, const uint8_t *payload, int32_t pl_ref,
-                               rxg_mbuf *const *m, uint8_t *handled, int *rc_out);
+                               uint32_t nrun, const struct asm_view *av, const uint8_t *payload,
+                               int32_t pl_ref, rxg_mbuf *const *m, uint8_t *handled, int *rc_out);
 static uint32_t host_segments(rxg_mbuf *const *m, uint32_t n, const rxg_verdict *v,
                               rxg_segment *sg);
 static int deliver_udp_batches(rxg_mbuf *const *m, const rxg_dgram *dg, const uint32_t *first,
@@ -1862,7 +1944,8 @@ int nstack_deliver(rxg_mbuf *const *m, uint32_t n, const rxg_verdict *v, uint64_
                  * mbufs (out of memory: arrival order, the segments one by one) */
                 rxg_tcp_run *run = NULL;
                 uint32_t nrun = 0;
-                uint32_t *sip = (g_gro || g_order) && k ? malloc((size_t)k * sizeof(*sip)) : NULL;
+                uint32_t *sip =
+                    (g_gro || g_order || g_assemble) && k ? malloc((size_t)k * sizeof(*sip)) : NULL;
                 if (sip)
                     for (uint32_t j = 0; j < k; j++) {
                         const rxg_mbuf *mb = m[sg[j].frame];
@@ -1871,7 +1954,7 @@ int nstack_deliver(rxg_mbuf *const *m, uint32_t n, const rxg_verdict *v, uint64_
                         for (uint32_t q = 0; q < 4; q++)
                             if (26u + q < mb->data_len) sip[j] |= (uint32_t)f[26u + q] << (8u * q);
                     }
-                if (sip && g_order) {
+                if (sip && (g_order || g_assemble)) { /* (assembly implies ordering) */
                     uint32_t *perm = malloc((size_t)k * sizeof(*perm)), moved = 0;
                     rxg_segment *so = malloc((size_t)k * sizeof(*so));
                     uint32_t *sipo = malloc((size_t)k * sizeof(*sipo));
@@ -1886,8 +1969,32 @@ int nstack_deliver(rxg_mbuf *const *m, uint32_t n, const rxg_verdict *v, uint64_
                 }
                 if (sip && g_gro) run = malloc((size_t)k * sizeof(*run));
                 if (run && rxg_tcp_runs_host(sg, sip, k, g_gro, run, &nrun) != RXG_OK) nrun = 0;
-                deliver_tcp_sorted(sg, k, nrun ? run : NULL, nrun, NULL, -1, m, s_handled, rc_out);
-                free(sip), free(run);
+                /* assembly: the streams by the rule's host restatement on the
+                 * ordered records, which then carry ncopy = take as the device's do
+                 * (out of memory: every TCP frame takes the frame-by-frame path,
+                 * which validates it on its own) */
+                struct asm_view av = {NULL, 0};
+                rxg_tcp_stream *stm = NULL;
+                if (g_assemble && k) {
+                    uint32_t *w = sip ? malloc((size_t)k * 4 * sizeof(*w)) : NULL, nst = 0;
+                    stm = w ? malloc((size_t)k * sizeof(*stm)) : NULL;
+                    if (stm) {
+                        for (uint32_t j = 0; j < k; j++) {
+                            const uint32_t cap = m[sg[j].frame]->data_len, from = 34u + 4u * sg[j].hl;
+                            w[j] = cap > from ? cap - from : 0u;
+                        }
+                        if (rxg_tcp_assemble_host(sg, sip, w, k, stm, &nst, w + k, w + 2 * k,
+                                                  w + 3 * k) == RXG_OK) {
+                            for (uint32_t j = 0; j < k; j++) sg[j].ncopy = (uint16_t)w[2 * k + j];
+                            av.st = stm, av.n = nst;
+                        }
+                    }
+                    free(w);
+                }
+                if (!g_assemble || av.st)
+                    deliver_tcp_sorted(sg, k, nrun ? run : NULL, nrun, av.st ? &av : NULL, NULL, -1, m,
+                                       s_handled, rc_out);
+                free(sip), free(run), free(stm);
                 done = s_handled;
             }
             free(sg);
@@ -2196,12 +2303,180 @@ static int deliver_tcp_conn(struct tcp_stream *s, const rxg_segment *sg, uint32_
     return 0;
 }
 
+/* deliver_tcp_conn's stream form (stream assembly on): the connection's k
+ * ordered records carry ncopy = take, and st[0..nst) are its streams
+ * (st[].first counted from sg - base), each one a contiguous byte range at
+ * st[].offset of the payload buffer.  The host rule of rxgpu.h ("TCP stream
+ * assembly") aligns every stream with rcv_nxt: one receive fragment of the
+ * fresh bytes (pointing into the held buffer when there is one, else copied;
+ * host verdicts: gathered from the frames, each record's skip passed over),
+ * the EOF fragment behind a FIN in sequence, and one ACK per stream; a stream
+ * behind a hole only draws an ACK.  LISTEN / SYN_RCVD / LAST_ACK keep the
+ * frame-by-frame path (tcp_dispatch validates each frame there). */
+static int deliver_tcp_conn_streams(struct tcp_stream *s, const rxg_segment *sg, uint32_t k,
+                                    const rxg_tcp_stream *st, uint32_t nst, uint32_t base,
+                                    const uint8_t *payload, int32_t pl_ref, rxg_mbuf *const *m,
+                                    uint8_t *handled, int *rc_out) {
+    if (s->status == TCP_STATUS_LISTEN || s->status == TCP_STATUS_SYN_RCVD ||
+        s->status == TCP_STATUS_LAST_ACK)
+        return 1;
+    for (uint32_t j = 0; j < k; j++) {
+        handled[sg[j].frame] = 1;
+        if (rc_out) rc_out[sg[j].frame] = RXG_RC_OK;
+    }
+    g_stat[2] += k;
+    if (s->status != TCP_STATUS_ESTABLISHED) return 0;
+    /* the fragments and ACKs the streams make, in order */
+    uint32_t nfr = 0, nack = 0, R = s->rcv_nxt;
+    uint64_t pbytes = 0;
+    for (uint32_t q = 0; q < nst; q++) {
+        const int fin = (st[q].flags & RXG_STREAM_FIN) != 0;
+        if (!st[q].bytes && !fin) continue; /* (pure ACKs) */
+        nack++;
+        const int32_t d = (int32_t)(R - st[q].seq);
+        if (d < 0) continue;
+        const uint32_t fresh = st[q].bytes > (uint32_t)d ? st[q].bytes - (uint32_t)d : 0;
+        if (fresh) nfr++, R += fresh, pbytes += pl_ref < 0 ? fresh : 0;
+        if (fin && (uint32_t)d <= st[q].bytes) {
+            nfr++;
+            break;
+        }
+    }
+    if (!nack) return 0;
+    pthread_mutex_lock(&s->mutex);
+    const uint32_t rroom = s->rq < D_RING_SIZE ? D_RING_SIZE - s->rq : 0;
+    const uint32_t aroom = s->sq < D_RING_SIZE ? D_RING_SIZE - s->sq : 0;
+    const uint32_t rtake = nfr < rroom ? nfr : rroom, atake = nack < aroom ? nack : aroom;
+    struct frag_batch *rb = NULL, *ab = NULL;
+    if (rtake) rb = bp_alloc(sizeof(*rb) + rtake * sizeof(struct tcp_fragment) + pbytes + 1);
+    if (atake) ab = bp_alloc(sizeof(*ab) + atake * sizeof(struct tcp_fragment));
+    for (int w = 0; w < 2; w++) {
+        struct frag_batch *b = w ? ab : rb;
+        if (!b) continue;
+        memset(&b->item, 0, sizeof(b->item));
+        b->item.batch = b;
+        b->n = w ? atake : rtake;
+        b->next = 0;
+        b->frag = (struct tcp_fragment *)(b + 1);
+        b->pl_ref = -1;
+    }
+    unsigned char *pp = rb ? (unsigned char *)(rb->frag + rtake) : NULL;
+    uint32_t fi = 0, ai = 0;
+    int closed = 0;
+    for (uint32_t q = 0; q < nst && !closed; q++) {
+        const rxg_tcp_stream *x = &st[q];
+        const rxg_segment *g = &sg[x->first - base], *gl = g + x->nseg - 1;
+        const int fin = (x->flags & RXG_STREAM_FIN) != 0;
+        /* payload a usable record carried and the device (or the host rule)
+         * passed over: already held by an earlier segment of the burst */
+        for (uint32_t j = 0; j < x->nseg; j++) {
+            const uint32_t from = 34u + 4u * g[j].hl, cap = m[g[j].frame]->data_len;
+            if (g[j].plen > 0 && !(g[j].flags & 0x06u) /* (not SYN, RST) */ && cap >= from &&
+                cap - from >= (uint32_t)g[j].plen)
+                g_asm_dup += (uint32_t)g[j].plen - g[j].ncopy;
+        }
+        if (!x->bytes && !fin) continue;
+        const int32_t d = (int32_t)(s->rcv_nxt - x->seq);
+        if (d >= 0) {
+            const uint32_t fresh = x->bytes > (uint32_t)d ? x->bytes - (uint32_t)d : 0;
+            g_asm_dup += x->bytes - fresh;
+            for (int eof = 0; eof < 2; eof++) {
+                if (eof ? !(fin && (uint32_t)d <= x->bytes) : !fresh) continue;
+                if (fi < rtake && rb) {
+                    struct tcp_fragment *fr = &rb->frag[fi];
+                    memset(fr, 0, sizeof(*fr));
+                    fr->dport = ntohs(g->dport);
+                    fr->sport = ntohs(g->sport);
+                    if (eof) {
+                        /* (the 0-length fragment: nrecv's EOF) */
+                    } else if (pl_ref >= 0) {
+                        fr->data = (unsigned char *)payload + x->offset + (uint32_t)d; /* (no copy) */
+                        fr->length = fresh;
+                        rb->pl_ref = pl_ref;
+                    } else {
+                        fr->data = pp;
+                        fr->length = fresh;
+                        if (payload) {
+                            memcpy(pp, payload + x->offset + (uint32_t)d, fresh);
+                        } else { /* (host verdicts: from the frames, skip passed over) */
+                            uint32_t pos = 0;
+                            for (uint32_t j = 0; j < x->nseg; j++) {
+                                const uint32_t t = g[j].ncopy, lo = pos > (uint32_t)d ? pos : (uint32_t)d;
+                                if (pos + t > lo) {
+                                    const rxg_mbuf *mb_ = m[g[j].frame];
+                                    memcpy(pp + (lo - (uint32_t)d),
+                                           (const uint8_t *)mb_->buf_addr + mb_->data_off + 34u +
+                                               4u * g[j].hl + ((uint32_t)g[j].plen - t) + (lo - pos),
+                                           pos + t - lo);
+                                }
+                                pos += t;
+                            }
+                        }
+                        pp += fresh;
+                        g_copied_bytes += fresh;
+                    }
+                    g_stat[4]++;
+                } else {
+                    g_stat[1]++;
+                }
+                fi++;
+                if (eof) {
+                    s->status = TCP_STATUS_CLOSE_WAIT;
+                    s->rcv_nxt += 1;
+                    closed = 1;
+                } else {
+                    s->rcv_nxt += fresh;
+                }
+            }
+            s->snd_nxt = x->ack;
+        } else {
+            g_asm_hole++;
+        }
+        if (ai < atake && ab) { /* ng_tcp_send_ackpkt, tcp.c:187-216 */
+            struct tcp_fragment *a = &ab->frag[ai];
+            memset(a, 0, sizeof(*a));
+            a->sport = gl->dport;
+            a->dport = gl->sport;
+            a->seqnum = s->snd_nxt;
+            a->acknum = s->rcv_nxt;
+            a->tcp_flags = TCP_ACK;
+            a->windows = D_TCP_INITIAL_WINDOW;
+            a->hdrlen_off = 0x50;
+        }
+        ai++;
+    }
+    if (rb) {
+        if (rb->pl_ref >= 0) { /* until the batch is freed */
+            rxg_payload_hold(g_ctx, rb->pl_ref);
+            atomic_fetch_add_explicit(&g_pl_batches, 1, memory_order_relaxed);
+            atomic_fetch_add_explicit(&g_pl_out[rb->pl_ref], 1, memory_order_relaxed);
+        }
+        if (ring_enqueue(s->rcvbuf, &rb->item)) { /* (not reached: items <= fragments <= capacity) */
+            frag_item_free(&rb->item);
+            g_stat[4] -= rtake, g_stat[1] += rtake;
+        } else {
+            cnt_set(&s->rq, s->rq + rtake);
+            pthread_cond_signal(&s->cond); /* tcp.c:178-180 */
+        }
+    }
+    if (ab) {
+        if (ring_enqueue(s->sndbuf, &ab->item))
+            bp_free(ab);
+        else
+            cnt_set(&s->sq, s->sq + atake);
+    }
+    pthread_mutex_unlock(&s->mutex);
+    if (closed) restate_tcb(s, 0);
+    return 0;
+}
+
 /* the sorted segments, connection by connection (g_lock held); frames of
  * connections that need the frame-by-frame path are left unmarked */
 static void deliver_tcp_sorted(const rxg_segment *sg, uint32_t nseg, const rxg_tcp_run *run,
-                               uint32_t nrun, const uint8_t *payload, int32_t pl_ref,
-                               rxg_mbuf *const *m, uint8_t *handled, int *rc_out) {
+                               uint32_t nrun, const struct asm_view *av, const uint8_t *payload,
+                               int32_t pl_ref, rxg_mbuf *const *m, uint8_t *handled, int *rc_out) {
     uint32_t r0 = 0; /* (coalescing) the first run of the connection: runs never span two */
+    uint32_t q0 = 0; /* (assembly) its first stream: streams never span two either */
     for (uint32_t a = 0, b; a < nseg; a = b) {
         b = a + 1;
         while (b < nseg && sg[b].flow == sg[a].flow) b++;
@@ -2215,10 +2490,17 @@ static void deliver_tcp_sorted(const rxg_segment *sg, uint32_t nseg, const rxg_t
         uint32_t r1 = r0;
         if (run)
             while (r1 < nrun && run[r1].first < b) r1++;
-        if (s)
+        uint32_t q1 = q0;
+        if (av)
+            while (q1 < av->n && av->st[q1].first < b) q1++;
+        if (s && av)
+            deliver_tcp_conn_streams(s, sg + a, b - a, av->st + q0, q1 - q0, a, payload, pl_ref, m,
+                                     handled, rc_out);
+        else if (s)
             deliver_tcp_conn(s, sg + a, b - a, run && r1 > r0 ? run + r0 : NULL, r1 - r0, a, payload,
                              pl_ref, m, handled, rc_out);
         r0 = r1;
+        q0 = q1;
     }
 }
 
@@ -2347,12 +2629,14 @@ static int deliver_part(rxg_mbuf *const *m, uint32_t k, const rxg_verdict *v, ui
     uint32_t nrun = 0;
     if (d->nseg && g_gro && rxg_delivery_runs(g_ctx, d, &run, &nrun) != RXG_OK) run = NULL, nrun = 0;
     uint32_t moved = 0; /* (ordering on at the submit: the records that moved) */
-    if (d->nseg && g_order && rxg_delivery_moved(g_ctx, d, &moved) == RXG_OK) g_order_moved += moved;
+    if (d->nseg && (g_order || g_assemble) && rxg_delivery_moved(g_ctx, d, &moved) == RXG_OK) g_order_moved += moved;
     rxg_ddos_summary dsum; /* (the detector on at the submit: the burst's summary) */
     if (g_ddos && rxg_delivery_ddos(g_ctx, d, &dsum) == RXG_OK) ddos_account(&dsum);
-    if (d->nseg)
-        deliver_tcp_sorted(d->seg, d->nseg, nrun ? run : NULL, nrun, d->tcp_payload,
-                           d->tcp_payload_ref, m, handled, rco);
+    struct asm_view av = {NULL, 0}; /* (assembly on at the submit: the burst's streams) */
+    if (d->nseg && g_assemble && rxg_delivery_streams(g_ctx, d, &av.st, &av.n) != RXG_OK) av.st = NULL;
+    if (d->nseg && (!g_assemble || av.st))
+        deliver_tcp_sorted(d->seg, d->nseg, nrun ? run : NULL, nrun, av.st ? &av : NULL,
+                           d->tcp_payload, d->tcp_payload_ref, m, handled, rco);
     const double t3 = mono_ms();
     delivered += deliver_burst(m, k, v, rco, handled);
     g_udp_done = 0;
@@ -2946,7 +3230,8 @@ int64_t nstack_drain_all_sum(void *buf, size_t cap, uint64_t *bytes, uint64_t *s
 int nstack_set_rx_gro(uint32_t W) {
     if (W > RXG_GRO_MAX_WINDOW) return RXG_EINVAL;
     pthread_mutex_lock(&g_lock);
-    int rc = W && g_inplace ? RXG_EINVAL : RXG_OK; /* (payloads left in their frames) */
+    /* (payloads left in their frames; assembled streams are coalesced already) */
+    int rc = W && (g_inplace || g_assemble) ? RXG_EINVAL : RXG_OK;
     if (rc == RXG_OK) {
         g_gro = W;
         if (g_ctx && !g_inplace) rc = rxg_tune_deliver(g_ctx, dlv_flags());
@@ -2958,7 +3243,7 @@ int nstack_set_rx_gro(uint32_t W) {
 
 int nstack_set_rx_inplace(int on, void (*release)(rxg_mbuf *m, void *arg), void *arg) {
     pthread_mutex_lock(&g_lock);
-    if (on && g_gro) { /* (coalesced payloads are gathered, not left in place) */
+    if (on && (g_gro || g_assemble)) { /* (coalesced payloads and streams are gathered) */
         pthread_mutex_unlock(&g_lock);
         return RXG_EINVAL;
     }
@@ -2974,6 +3259,17 @@ int nstack_set_rx_order(int on) {
     pthread_mutex_lock(&g_lock);
     g_order = on != 0;
     const int rc = g_ctx ? rxg_tune_deliver(g_ctx, dlv_flags()) : RXG_OK;
+    pthread_mutex_unlock(&g_lock);
+    return rc;
+}
+
+int nstack_set_rx_assemble(int on) {
+    pthread_mutex_lock(&g_lock);
+    int rc = on && (g_gro || g_inplace) ? RXG_EINVAL : RXG_OK;
+    if (rc == RXG_OK) {
+        g_assemble = on != 0;
+        if (g_ctx) rc = rxg_tune_deliver(g_ctx, dlv_flags());
+    }
     pthread_mutex_unlock(&g_lock);
     return rc;
 }
@@ -3440,14 +3736,17 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
 }
 
 uint64_t nstack_stat(int which) {
-    if (which < 0 || which > 18) return 0;
+    if (which < 0 || which > 20) return 0;
     if (which >= 15) { /* segments absorbed by receive coalescing / moved by ordering; the
-                          flood detector's frames under alarm / rises */
+                          flood detector's frames under alarm / rises; stream assembly's
+                          bytes already received / streams behind a hole */
         pthread_mutex_lock(&g_lock);
         const uint64_t a = which == 15   ? g_gro_absorbed
                            : which == 16 ? g_order_moved
                            : which == 17 ? g_ddos_acc.alarm_frames
-                                         : g_ddos_acc.rises;
+                           : which == 18 ? g_ddos_acc.rises
+                           : which == 19 ? g_asm_dup
+                                         : g_asm_hole;
         pthread_mutex_unlock(&g_lock);
         return a;
     }

@@ -128,6 +128,13 @@ NSTACK_DDOS_DTYPE = np.dtype([("frames_seen", "<u8"), ("rises", "<u8"), ("falls"
 assert TCP_RUN_DTYPE.itemsize == 16
 GRO_MAX_WINDOW, GRO_DEFAULT_WINDOW = 1 << 20, 65536
 DLV_TCP_IN_PLACE, DLV_TCP_GRO, DLV_TCP_ORDER = 0x1, 0x2, 0x4
+DLV_TCP_ASSEMBLE = 0x20
+# rxg_tcp_stream, a contiguous byte range of one connection (stream assembly)
+TCP_STREAM_DTYPE = np.dtype([("first", "<u4"), ("nseg", "<u4"), ("seq", "<u4"), ("ack", "<u4"),
+                             ("bytes", "<u4"), ("offset", "<u4"), ("flags", "<u4"),
+                             ("reserved", "<u4")])
+assert TCP_STREAM_DTYPE.itemsize == 32
+STREAM_FIN, STREAM_HOLE = 0x1, 0x2
 # rxg_txd, the send descriptor of the TX encoder (K5): sip/dip/sport/dport/
 # window/urp raw as the reference stores them, seq/ack host order
 TXD_DTYPE = np.dtype([("dst_mac", "u1", (6,)), ("src_mac", "u1", (6,)), ("sip", "<u4"), ("dip", "<u4"),
@@ -203,6 +210,11 @@ _tcp_compact_ordered_dev = _sig("rxg_tcp_compact_ordered_dev", _i32, _vp, _vp, _
                                 _vp, _u32, _vp, _vp, _vp, _u64, _vp, _vp)
 _tcp_order_host = _sig("rxg_tcp_order_host", _i32, _vp, _vp, _u32, _vp, C.POINTER(_u32))
 _delivery_moved = _sig("rxg_delivery_moved", _i32, _vp, _vp, C.POINTER(_u32))
+_tcp_assemble_dev = _sig("rxg_tcp_assemble_dev", _i32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp,
+                         _vp, _u64, _vp, _vp)
+_tcp_assemble_host = _sig("rxg_tcp_assemble_host", _i32, _vp, _vp, _vp, _u32, _vp, C.POINTER(_u32),
+                          _vp, _vp, _vp)
+_delivery_streams = _sig("rxg_delivery_streams", _i32, _vp, _vp, C.POINTER(_vp), C.POINTER(_u32))
 _f64 = C.c_double
 _ddos_dev = _sig("rxg_ddos_dev", _i32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _f64, _vp, _vp, _vp, _vp,
                  _vp, _vp)
@@ -304,7 +316,8 @@ EXPORTED = ["rxg_open", "rxg_close", "rxg_strerror", "rxg_last_hip_error", "rxg_
             "rxg_flows_commit", "rxg_num_udp_ids", "rxg_flows_rebuilds", "rxg_udp_compact_dev",
             "rxg_process_mbufs_udp", "rxg_tcp_compact_dev", "rxg_tcp_coalesce_dev",
             "rxg_tcp_runs_host", "rxg_tcp_compact_ordered_dev", "rxg_tcp_order_host",
-            "rxg_delivery_moved", "rxg_tune_deliver", "rxg_tune_gro", "rxg_delivery_runs",
+            "rxg_delivery_moved", "rxg_tcp_assemble_dev", "rxg_tcp_assemble_host",
+            "rxg_delivery_streams", "rxg_tune_deliver", "rxg_tune_gro", "rxg_delivery_runs",
             "rxg_process_mbufs_deliver",
             "rxg_deliver_submit", "rxg_deliver_wait", "rxg_tune_ingest",
             "rxg_register_host", "rxg_unregister_host", "rxg_payload_hold", "rxg_payload_release",
@@ -580,6 +593,30 @@ class Context:
         _check(_delivery_moved(self._h, C.byref(d), C.byref(mv)), "rxg_delivery_moved")
         return mv.value
 
+    def tcp_assemble_dev(self, d_pkts, d_off, d_len, n: int, off_unit_log2: int, d_v, d_seg,
+                         d_stream, d_payload, payload_cap: int, d_totals, stream=None):
+        """the sort, the ordering stage and the stream assembly
+        (rxg_tcp_assemble_dev), async on stream; d_stream: room for n
+        TCP_STREAM_DTYPE records; d_totals: 6 words {segments, payload bytes,
+        overflow, streams, moved, sum of skip}"""
+        def p(x):
+            return x if (x is None or isinstance(x, int)) else x.data_ptr()
+        _check(_tcp_assemble_dev(self._h, p(d_pkts), p(d_off), p(d_len), n, off_unit_log2, p(d_v),
+                                 p(d_seg), p(d_stream), p(d_payload), payload_cap, p(d_totals),
+                                 stream), "rxg_tcp_assemble_dev")
+
+    def delivery_streams(self, handle) -> np.ndarray:
+        """rxg_delivery_streams of a waited-for deliver_submit handle: a copy of
+        the burst's streams (empty with DLV_TCP_ASSEMBLE off)"""
+        _, _, d = handle
+        ptr, n = _vp(), _u32()
+        _check(_delivery_streams(self._h, C.byref(d), C.byref(ptr), C.byref(n)),
+               "rxg_delivery_streams")
+        if not ptr.value or not n.value:
+            return np.zeros(0, TCP_STREAM_DTYPE)
+        return np.frombuffer((C.c_uint8 * (32 * n.value)).from_address(ptr.value),
+                             np.uint8).copy().view(TCP_STREAM_DTYPE)
+
     def ddos_dev(self, d_pkts, d_off, d_len, n: int, off_unit_log2: int, len_hint: int,
                  thresh: float, d_state, d_bits, d_flag, d_stat, d_summary, stream=None):
         """rxg_ddos_dev: one burst through the entropy flood detector, async on
@@ -630,7 +667,8 @@ class Context:
 
     def tune_deliver(self, flags: int):
         """rxg_tune_deliver: DLV_TCP_IN_PLACE or DLV_TCP_GRO, either with
-        DLV_TCP_ORDER, any of them with DLV_DDOS (0 = the default)"""
+        DLV_TCP_ORDER; or DLV_TCP_ASSEMBLE (with or without DLV_TCP_ORDER); any
+        of them with DLV_DDOS (0 = the default)"""
         _check(_tune_deliver(self._h, flags), "rxg_tune_deliver")
 
     def tune_gro(self, window: int):
@@ -960,6 +998,26 @@ def tcp_order_host(seg: np.ndarray, sip: np.ndarray):
     return perm[:n].copy(), moved.value
 
 
+def tcp_assemble_host(seg: np.ndarray, sip: np.ndarray, avail: np.ndarray):
+    """rxg_tcp_assemble_host: the stream assembly of ordered records (seg,
+    SEGMENT_DTYPE), their raw source addresses and captured payload bytes, on
+    the CPU: (streams, skip, take, dst)"""
+    seg = np.ascontiguousarray(seg, SEGMENT_DTYPE)
+    sip = np.ascontiguousarray(sip, np.uint32)
+    avail = np.ascontiguousarray(avail, np.uint32)
+    assert len(seg) == len(sip) == len(avail)
+    n = len(seg)
+    if not n: # (the call takes no NULL, and numpy's empty arrays may have one)
+        seg, sip, avail = np.zeros(1, SEGMENT_DTYPE), np.zeros(1, np.uint32), np.zeros(1, np.uint32)
+    st = np.zeros(max(n, 1), TCP_STREAM_DTYPE)
+    skip, take, dst = (np.zeros(max(n, 1), np.uint32) for _ in range(3))
+    nst = _u32()
+    _check(_tcp_assemble_host(seg.ctypes.data, sip.ctypes.data, avail.ctypes.data, n, st.ctypes.data,
+                              C.byref(nst), skip.ctypes.data, take.ctypes.data, dst.ctypes.data),
+           "rxg_tcp_assemble_host")
+    return st[:nst.value].copy(), skip[:n].copy(), take[:n].copy(), dst[:n].copy()
+
+
 def tx_encode_tso_host(txd: np.ndarray, payload: np.ndarray, mss: int, cap_bytes: int, out_cap: int,
                        slot_bytes: int = 0, flags: int = 0, fill: int = 0, fill_entries: int = 0):
     """rxg_tx_encode_tso_host, the TX encoder with TCP segmentation on the CPU:
@@ -1146,6 +1204,7 @@ class NStack:
                    ("nstack_set_tx_mss", _i32, [_u32]),
                    ("nstack_set_rx_gro", _i32, [_u32]),
                    ("nstack_set_rx_order", _i32, [_i32]),
+                   ("nstack_set_rx_assemble", _i32, [_i32]),
                    ("nstack_set_rx_ddos", _i32, [_i32, C.c_double]),
                    ("nstack_ddos_status", _i32, [_vp])]
             for name, res, args in sig:
@@ -1456,6 +1515,14 @@ class NStack:
         one receive fragment and one ACK per run of at most about `window` bytes
         (0 = off); raises RxgError (RXG_EINVAL) while in-place receive is on"""
         _check(self.lib.nstack_set_rx_gro(window), "nstack_set_rx_gro")
+
+    def set_rx_assemble(self, on: bool):
+        """nstack_set_rx_assemble: each connection's burst assembled into
+        contiguous byte ranges and aligned with rcv_nxt (duplicates dropped,
+        overlaps trimmed, a stop at every hole); raises RxgError (RXG_EINVAL)
+        while coalescing or in-place receive is on; stat(19) / stat(20) count
+        the bytes discarded as already received / the ranges behind a hole"""
+        _check(self.lib.nstack_set_rx_assemble(1 if on else 0), "nstack_set_rx_assemble")
 
     def set_rx_order(self, on: bool):
         """nstack_set_rx_order: a burst's segments reach each connection in

@@ -275,8 +275,33 @@ int nstack_set_rx_gro(uint32_t W);
  * because the lists changed under it (nstack_stat(5)) keeps arrival order.
  * This reorders what a burst holds; it validates nothing: duplicates are not
  * dropped, a hole is not waited for, and data of segments without PSH is not
- * delivered.  TCP here is not loss-safe with it. */
+ * delivered.  TCP here is not loss-safe with it: that is
+ * nstack_set_rx_assemble, below. */
 int nstack_set_rx_order(int on);
+/* TCP stream assembly: the receive side made loss-safe (the rule and the host
+ * rule: rxgpu.h, "TCP stream assembly").  on == 0 (the default): the paths
+ * above.  on != 0: a connection's segments of a burst are ordered (as with
+ * nstack_set_rx_order, whether that is on or not) and assembled into
+ * contiguous byte ranges: duplicates dropped, overlaps trimmed, data counted
+ * with or without PSH, a new range at every hole.  Each range is then aligned
+ * with the connection's rcv_nxt: bytes below it are passed over, a range that
+ * starts above it (data behind a hole) is ignored and answered with an ACK of
+ * rcv_nxt.  One receive fragment and one ACK per connection per burst,
+ * whatever the segmentation.  The device paths (nstack_rx_burst, the halves,
+ * nstack_rx_submit / nstack_rx_complete) set RXG_DLV_TCP_ASSEMBLE, with the
+ * pooled payload buffers as before; the host-verdict path (nstack_deliver)
+ * applies rxg_tcp_order_host and rxg_tcp_assemble_host and copies from the
+ * frames.  A frame delivered on the frame-by-frame path to an ESTABLISHED
+ * connection (a burst whose lists changed under it, nstack_stat(5)) is
+ * validated as a range of one.  Connections in LISTEN / SYN_RCVD / LAST_ACK
+ * keep today's path.  RXG_EINVAL while nstack_set_rx_gro or
+ * nstack_set_rx_inplace is on, and those two are RXG_EINVAL while this is on.
+ * nstack_stat(19) adds up the payload bytes discarded as already received,
+ * nstack_stat(20) the ranges ignored behind a hole.
+ * Limits: there is no reassembly queue across bursts (data behind a hole is
+ * dropped and must be retransmitted), and the send side still has no
+ * retransmission. */
+int nstack_set_rx_assemble(int on);
 /* The reference's entropy flood detector over the received frames (the rule:
  * rxgpu.h, "Entropy flood detector"; ddos_detect in the reference's I/O loop,
  * before the burst goes into the protocol ring).  on == 0 (the default): off.
@@ -354,7 +379,9 @@ int nstack_set_halves(uint32_t min_half);
  * pass (nstack_set_tx_mss); 15 = segments absorbed into a preceding segment's
  * receive fragment (nstack_set_rx_gro); 16 = segment records moved by sequence
  * ordering (nstack_set_rx_order); 17 = frames received under the flood detector's
- * alarm, 18 = its rises (nstack_set_rx_ddos).  Counter 1 also counts TX items dropped (a
+ * alarm, 18 = its rises (nstack_set_rx_ddos); 19 = payload bytes discarded as
+ * already received, 20 = streams ignored behind a hole
+ * (nstack_set_rx_assemble).  Counter 1 also counts TX items dropped (a
  * send ring full, or a datagram too long for a frame). */
 uint64_t nstack_stat(int which);
 

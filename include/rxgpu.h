@@ -471,8 +471,9 @@ int rxg_tcp_runs_host(const rxg_segment *seg, const uint32_t *sip, uint32_t nseg
  * writes it, with moved = 0.
  * This is reordering, not sequence validation: duplicates are not dropped,
  * nothing stops at a hole, and data of segments without PSH is still not
- * delivered (the reference's PSH-only rule).  Validation is a follow-up on the
- * host; the option does NOT make TCP here loss-safe.
+ * delivered (the reference's PSH-only rule).  Validation is the stream
+ * assembly below ("TCP stream assembly"); this option alone does NOT make TCP
+ * here loss-safe.
  *
  * One device call for both forms, asynchronous on `stream`.  W == 0:
  * rxg_tcp_compact_dev's outputs (records and gather) in the new order; d_run
@@ -494,6 +495,99 @@ int rxg_tcp_compact_ordered_dev(rxg_ctx *ctx, const uint8_t *d_pkts, const uint3
  * never fall back to it. */
 int rxg_tcp_order_host(const rxg_segment *seg, const uint32_t *sip, uint32_t nseg, uint32_t *perm,
                        uint32_t *moved);
+
+/* ---- TCP stream assembly: duplicates dropped, overlaps trimmed, a stop at
+ * every hole (opt-in)
+ * Ordering alone validates nothing: the state machine never compares a
+ * segment's seq with rcv_nxt, so a retransmitted duplicate is delivered twice,
+ * an overlapping retransmit delivers the overlap twice, a lost segment shifts
+ * the byte stream, and data on a segment without PSH is dropped without being
+ * counted.  After the sort and the ordering stage a connection's segments of
+ * a burst are adjacent and in sequence order: which of their bytes are new is
+ * a segmented running maximum, and laying them down once, contiguously, is a
+ * trimmed gather.  Neither needs rcv_nxt, so the device assembles each
+ * connection's burst into contiguous byte ranges ("streams") and the host,
+ * which owns rcv_nxt, aligns each stream with one subtraction.
+ * The rule.  Input: the records seg[0..nseg) exactly as
+ * rxg_tcp_compact_ordered_dev with W = 0 orders them, each record's raw source
+ * address sip (frame bytes 26-29, 0 past the capture) and avail[j], the
+ * captured bytes past its TCP header: max(0, caplen - 34 - 4*hl).
+ *   Groups: the ordering rule's: a maximal range of consecutive records with
+ *   (flags & 0x06) == 0 and equal flow, sip, sport and dport.  A SYN or RST
+ *   record is a group of one and is left alone: one stream, bytes 0, no FIN.
+ *   Data length: usable(j): plen <= 0 or avail >= plen.  dlen[j] = plen if
+ *   plen > 0 and usable, else 0.  Data counts with or without PSH.  A record
+ *   whose payload was not captured whole contributes nothing, and its FIN is
+ *   ignored.
+ *   Positions, in a group with first record h (in output order):
+ *     a[j] = (uint32_t)(seq[j] - seq[h]);  end[j] = a[j] + dlen[j];
+ *     cov[j] = the maximum of end[i] over the group's records before j, 0 at h.
+ *   All positions are 64-bit, so the rule is total for any input.
+ *   New bytes: ns[j] = max(a[j], cov[j]); take[j] = end[j] - min(end[j], ns[j]);
+ *   the payload bytes skipped at the front are skip[j] = dlen[j] - take[j].
+ *   FIN: finok[j] = FIN set, usable and end[j] >= cov[j].
+ *   Streams: record j starts a stream iff it starts its group, or
+ *   a[j] > cov[j] (a hole), or finok[j-1] holds in the same group.  A stream
+ *   with head p has seq = seq[h] + ns[p] (mod 2^32), bytes = the sum of take
+ *   over its records, RXG_STREAM_FIN iff a finok in it (only its last record
+ *   can have one), ack = the ack of its last record, first, nseg, and
+ *   RXG_STREAM_HOLE when a hole started it.  Inside a stream the taken ranges
+ *   are disjoint and contiguous: record j's bytes go to stream offset
+ *   ns[j] - ns[p].  Where two segments carry the same byte, the one first in
+ *   sequence order wins.
+ *   Layout: the coalescing form's: streams in order in the payload buffer,
+ *   each at the 16-B-rounded end of the one before, the pad bytes written as
+ *   0; a stream that would pass payload_cap sets the overflow flag and is not
+ *   written; no other byte is touched.
+ * The host rule, for an ESTABLISHED tcb with rcv_nxt = R, streams in order,
+ * d = (int32_t)(R - seq):
+ *   d < 0: data behind a hole; nothing is delivered, one ACK with acknum R;
+ *   d >= 0: fresh = bytes > d ? bytes - d : 0.  If fresh: one receive fragment
+ *   of fresh bytes starting d bytes into the stream, R += fresh.  If FIN and
+ *   d <= bytes: the EOF fragment, R += 1, CLOSE_WAIT (later streams are
+ *   ignored).  If the stream had bytes or a FIN: snd_nxt = ack, one ACK with
+ *   acknum R.  A stream with no bytes and no FIN (pure ACKs) queues nothing.
+ * Over every R this delivers exactly the byte ranges, the final rcv_nxt and
+ * the EOF of a sequential receiver without an out-of-order buffer that takes
+ * the same records one at a time: one fragment and one ACK per connection per
+ * burst, whatever the segmentation, PSH flags, duplicates or overlaps.
+ * Limits: there is no reassembly queue across bursts (data behind a hole is
+ * dropped and must be retransmitted), and the send side has no retransmission. */
+typedef struct rxg_tcp_stream {
+    uint32_t first;    /* index of the stream's first record */
+    uint32_t nseg;     /* records in the stream */
+    uint32_t seq;      /* sequence number of the stream's first byte */
+    uint32_t ack;      /* the ack of its last record */
+    uint32_t bytes;    /* new bytes: the sum of take over its records */
+    uint32_t offset;   /* the stream's start in the payload buffer (16-B aligned) */
+    uint32_t flags;    /* RXG_STREAM_* */
+    uint32_t reserved; /* 0 */
+} rxg_tcp_stream;      /* 32 bytes */
+#define RXG_STREAM_FIN 0x1u
+#define RXG_STREAM_HOLE 0x2u
+/* Device form, asynchronous on `stream`: the sort, the ordering stage and the
+ * assembly.  d_seg (room for n) gets the ordered form's records, except that
+ * ncopy = take and offset = where those bytes lie in d_payload (the stream's
+ * offset + ns[j] - ns[p], any byte phase).  d_stream (room for n) gets the
+ * streams in order.  d_totals (6 words) = {segments, payload bytes used (the
+ * 16-B-rounded end of the last stream), 1 if payload_cap was too small,
+ * streams, moved (the ordering stage's), the sum of skip mod 2^32}.
+ * d_payload NULL is RXG_EINVAL; n == 0 or an empty tcb id space zeroes the
+ * totals.  The device workspace grows on demand (stream-ordered). */
+int rxg_tcp_assemble_dev(rxg_ctx *ctx, const uint8_t *d_pkts, const uint32_t *d_off,
+                         const uint16_t *d_len, uint32_t n, uint32_t off_unit_log2,
+                         const rxg_verdict *d_v, rxg_segment *d_seg, rxg_tcp_stream *d_stream,
+                         uint8_t *d_payload, uint64_t payload_cap, uint32_t *d_totals, void *stream);
+/* The same rule on already ordered records in host memory (no device, no
+ * context): stream (room for nseg) gets the streams, offset as the device
+ * lays them out, *nstream their count; skip / take / dst (room for nseg each)
+ * get every record's skipped and taken bytes and the offset of its taken
+ * bytes in that layout.  seg is not modified.  nseg == 0 is valid; a NULL
+ * argument is RXG_EINVAL.  The CPU path and the tests' second opinion; the
+ * device call never falls back to it. */
+int rxg_tcp_assemble_host(const rxg_segment *seg, const uint32_t *sip, const uint32_t *avail,
+                          uint32_t nseg, rxg_tcp_stream *stream, uint32_t *nstream, uint32_t *skip,
+                          uint32_t *take, uint32_t *dst);
 
 /* One mbuf burst through the whole device half of delivery: classify
  * (rxg_process_mbufs), then the UDP compaction (when the UDP id space is at
@@ -567,8 +661,23 @@ int rxg_deliver_wait(rxg_ctx *ctx, rxg_delivery *d, float ms[8]);
  * rxg_delivery_moved reports the burst's count of moved records.  Off by
  * default. */
 #define RXG_DLV_TCP_ORDER 0x4u
+/* RXG_DLV_TCP_ASSEMBLE: the TCP half of a delivery burst runs the stream
+ * assembly (rxg_tcp_assemble_dev; the rule: "TCP stream assembly").  It
+ * implies ordering: with RXG_DLV_TCP_ORDER it behaves the same.  Not with
+ * RXG_DLV_TCP_GRO or RXG_DLV_TCP_IN_PLACE (RXG_EINVAL): the streams are the
+ * coalesced form, and they are gathered.  May be combined with RXG_DLV_DDOS.
+ * struct rxg_delivery is unchanged (seg[].ncopy = take, offset into
+ * tcp_payload); the streams cross PCIe with the records
+ * (rxg_delivery_streams), rxg_delivery_moved keeps working, and the pooled
+ * payload buffers work unchanged.  Off by default.  (0x8 is not a flag.) */
+#define RXG_DLV_TCP_ASSEMBLE 0x20u
 int rxg_tune_deliver(rxg_ctx *ctx, uint32_t flags);
 int rxg_tune_gro(rxg_ctx *ctx, uint32_t W);
+/* The streams of a waited-for delivery burst: *stream / *nstream, valid as
+ * long as the burst's delivery set is; NULL / 0 when RXG_DLV_TCP_ASSEMBLE was
+ * off for it. */
+int rxg_delivery_streams(rxg_ctx *ctx, const rxg_delivery *d, const rxg_tcp_stream **stream,
+                         uint32_t *nstream);
 /* The runs of a waited-for delivery burst: *run / *nrun, valid as long as the
  * burst's delivery set is; NULL / 0 when RXG_DLV_TCP_GRO was off for it. */
 int rxg_delivery_runs(rxg_ctx *ctx, const rxg_delivery *d, const rxg_tcp_run **run,
