@@ -96,6 +96,11 @@ hipError_t rx_assemble_launch(const uint8_t *pkts, const uint32_t *off, const ui
                               uint32_t n, uint32_t unit_log2, const uint4 *verd, uint32_t nt,
                               rxg_segment *seg, rxg_tcp_stream *stream, uint8_t *payload,
                               uint64_t cap, uint32_t *totals, void *ws, hipStream_t s);
+size_t rx_syncookie_ws_bytes(uint32_t n);
+hipError_t rx_syncookie_launch(const uint8_t *pkts, const uint32_t *off, const uint16_t *len, uint32_t n,
+                               uint32_t unit_log2, const uint4 *verd, const uint32_t *lmask,
+                               uint32_t id_space, const rxg_ck_params *p, uint8_t *status, rxg_txd *txd,
+                               uint32_t *totals, void *ws, hipStream_t s);
 size_t rx_compact_ws_bytes(uint32_t n, uint32_t nflows);
 hipError_t rx_compact_launch(const uint8_t *pkts, const uint32_t *off, const uint16_t *len,
                              uint32_t n, uint32_t unit_log2, const uint4 *verd, uint32_t nflows,
@@ -234,6 +239,21 @@ struct rxg_ctx {
     size_t d_ddos_ws_cap = 0;
     rxg_ddos_state *d_ddos_state = nullptr;
     rxg_ddos_summary *d_ddos_sum = nullptr;
+    // SYN cookies (K7, rx_syncookie.hip): the workspace of every call on this
+    // context; for the delivery bursts (RXG_DLV_SYNCOOKIE) the parameters and
+    // listener mask of rxg_syncookie_set (ck_hmask: the upload's source, kept
+    // until ev_ck says it has been read) and the device results
+    void *d_ck_ws = nullptr;
+    size_t d_ck_ws_cap = 0;
+    rxg_ck_params ck_p{};
+    uint32_t ck_id_space = 0;
+    std::vector<uint32_t> ck_hmask;
+    void *d_ck_mask = nullptr;
+    size_t d_ck_mask_cap = 0;
+    hipEvent_t ev_ck = nullptr;
+    uint8_t *d_ck_status = nullptr;
+    rxg_txd *d_ck_txd = nullptr;
+    uint32_t *d_ck_totals = nullptr;
     rx_ft_dev ft{};
     uint32_t tune_g = 0, tune_p = 0, tune_fpg = 0, tune_pipe = ~0u; // rxg_tune override
     uint32_t tune_bpc = 0; // rxg_tune_grid: resident blocks per CU cap (0 = occupancy)
@@ -329,6 +349,10 @@ struct rxg_ctx {
     struct delivery_set {
         bool on = false, udp = false, tcp = false, gro = false, order = false, ddos = false;
         bool assemble = false;
+        bool cookie = false;           // (rxg_delivery_cookies)
+        uint8_t *h_ck_status = nullptr;
+        rxg_txd *h_ck_txd = nullptr;
+        uint32_t *h_ck_totals = nullptr;
         uint32_t nstream = 0;          // (rxg_delivery_streams)
         rxg_tcp_stream *h_ss_stream = nullptr;
         rxg_ddos_summary *h_ddos = nullptr; // (rxg_delivery_ddos)
@@ -812,11 +836,18 @@ void rxg_close(rxg_ctx *c) {
     (void)hipFree(c->d_ddos_ws);
     (void)hipFree(c->d_ddos_state);
     (void)hipFree(c->d_ddos_sum);
+    (void)hipFree(c->d_ck_ws);
+    (void)hipFree(c->d_ck_mask);
+    (void)hipFree(c->d_ck_status);
+    (void)hipFree(c->d_ck_txd);
+    (void)hipFree(c->d_ck_totals);
+    if (c->ev_ck) (void)hipEventDestroy(c->ev_ck);
     for (rxg_ctx::delivery_set &ds : c->dls) {
         for (void *h : {(void *)ds.h_cp_dg, (void *)ds.h_cp_first, (void *)ds.h_cp_totals,
                         (void *)ds.h_cp_payload, (void *)ds.h_ss_seg, (void *)ds.h_ss_payload,
                         (void *)ds.h_ss_totals, (void *)ds.h_ss_run, (void *)ds.h_ss_stream,
-                        (void *)ds.h_ddos})
+                        (void *)ds.h_ddos, (void *)ds.h_ck_status, (void *)ds.h_ck_txd,
+                        (void *)ds.h_ck_totals})
             if (h) (void)hipHostFree(h);
         for (hipEvent_t e : ds.tev)
             if (e) (void)hipEventDestroy(e);
@@ -1212,7 +1243,7 @@ int rxg_tune_tables(rxg_ctx *c, uint32_t flags) {
 
 int rxg_tune_deliver(rxg_ctx *c, uint32_t flags) {
     if (!c || (flags & ~(RXG_DLV_TCP_IN_PLACE | RXG_DLV_TCP_GRO | RXG_DLV_TCP_ORDER | RXG_DLV_DDOS |
-                         RXG_DLV_TCP_ASSEMBLE)))
+                         RXG_DLV_TCP_ASSEMBLE | RXG_DLV_SYNCOOKIE)))
         return RXG_EINVAL;
     // (payloads that stay in their frames cannot be made contiguous)
     if ((flags & RXG_DLV_TCP_IN_PLACE) && (flags & RXG_DLV_TCP_GRO)) return RXG_EINVAL;
@@ -2029,6 +2060,96 @@ int rxg_delivery_streams(rxg_ctx *c, const rxg_delivery *d, const rxg_tcp_stream
     return RXG_OK;
 }
 
+// K7's three launches on s; the context's workspace is grown first.  An empty
+// call (no frame, or no listener id) zeroes its outputs without a launch.
+static int syncookie_impl(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off, const uint16_t *d_len,
+                          uint32_t n, uint32_t off_unit_log2, const uint4 *d_v, const uint32_t *d_lmask,
+                          uint32_t id_space, const rxg_ck_params *p, uint8_t *d_status, rxg_txd *d_txd,
+                          uint32_t *d_totals, hipStream_t s) {
+    if (n == 0 || id_space == 0) {
+        HIPCHK(hipMemsetAsync(d_totals, 0, 4 * sizeof(uint32_t), s));
+        if (n) HIPCHK(hipMemsetAsync(d_status, 0, n, s));
+        return RXG_OK;
+    }
+    const size_t ws = rx_syncookie_ws_bytes(n);
+    if (ws > c->d_ck_ws_cap) { // (its uses are ordered by the caller: freed and grown in stream order)
+        int rc = ensure_dev_async(&c->d_ck_ws, &c->d_ck_ws_cap, ws, s);
+        if (rc) return rc;
+    }
+    HIPCHK(rx_syncookie_launch(d_pkts, d_off, d_len, n, off_unit_log2, d_v, d_lmask, id_space, p,
+                               d_status, d_txd, d_totals, c->d_ck_ws, s));
+    return RXG_OK;
+}
+
+int rxg_syncookie_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off, const uint16_t *d_len,
+                      uint32_t n, uint32_t off_unit_log2, const rxg_verdict *d_v,
+                      const uint32_t *d_lmask, uint32_t id_space, const rxg_ck_params *p,
+                      uint8_t *d_status, rxg_txd *d_txd, uint32_t *d_totals, void *stream) {
+    if (!c || !p || !d_totals || p->max_age > 255u) return RXG_EINVAL;
+    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
+    if (n && (!d_pkts || !d_off || !d_len || !d_v || !d_status || !d_txd)) return RXG_EINVAL;
+    if ((id_space && !d_lmask) || ((uintptr_t)d_txd & 15u)) return RXG_EINVAL;
+    if (off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
+    DEVGUARD(c);
+    return syncookie_impl(c, d_pkts, d_off, d_len, n, off_unit_log2,
+                          reinterpret_cast<const uint4 *>(d_v), d_lmask, id_space, p, d_status, d_txd,
+                          d_totals, (hipStream_t)stream);
+}
+
+// the parameters, and the listeners as a bit mask on the device: uploaded on
+// the context's stream, so every burst submitted later sees it
+int rxg_syncookie_set(rxg_ctx *c, const rxg_ck_params *p, const uint32_t *listener_ids, uint32_t nl) {
+    if (!c || !p || p->max_age > 255u || (nl && !listener_ids)) return RXG_EINVAL;
+    uint32_t space = 0;
+    for (uint32_t k = 0; k < nl; ++k) {
+        if (listener_ids[k] == RXG_FLOW_NONE) return RXG_EINVAL;
+        if (listener_ids[k] >= space) space = listener_ids[k] + 1u;
+    }
+    if (c->device == RXG_HOST_ONLY) {
+        c->ck_p = *p;
+        c->ck_id_space = space;
+        return RXG_OK;
+    }
+    DEVGUARD(c);
+    if (!c->ev_ck) HIPCHK(hipEventCreateWithFlags(&c->ev_ck, hipEventDisableTiming));
+    else HIPCHK(hipEventSynchronize(c->ev_ck)); // (the last upload has read ck_hmask)
+    const size_t words = ((size_t)space + 31) / 32;
+    c->ck_hmask.assign(words, 0u);
+    for (uint32_t k = 0; k < nl; ++k) c->ck_hmask[listener_ids[k] >> 5] |= 1u << (listener_ids[k] & 31u);
+    if (words) {
+        int rc = ensure_dev_async(&c->d_ck_mask, &c->d_ck_mask_cap, words * sizeof(uint32_t), c->stream);
+        if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(c->d_ck_mask, c->ck_hmask.data(), words * sizeof(uint32_t),
+                              hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(hipEventRecord(c->ev_ck, c->stream));
+    c->ck_p = *p;
+    c->ck_id_space = space;
+    return RXG_OK;
+}
+
+int rxg_syncookie_tick(rxg_ctx *c, uint32_t t) {
+    if (!c) return RXG_EINVAL;
+    c->ck_p.t = t;
+    return RXG_OK;
+}
+
+int rxg_delivery_cookies(rxg_ctx *c, const rxg_delivery *d, const uint8_t **status,
+                         const rxg_txd **txd, uint32_t *ntxd, uint32_t totals[4]) {
+    if (!c || !d || !status || !txd || !ntxd || !totals) return RXG_EINVAL;
+    *status = nullptr, *txd = nullptr, *ntxd = 0;
+    memset(totals, 0, 4 * sizeof(uint32_t));
+    if (d->set < 1 || d->set > RXG_DELIVER_DEPTH) return RXG_EINVAL;
+    const rxg_ctx::delivery_set &ds = c->dls[d->set - 1];
+    if (ds.on) return RXG_EINVAL; // (not waited for yet)
+    if (!ds.cookie) return RXG_OK;
+    *status = ds.h_ck_status;
+    *txd = ds.h_ck_txd;
+    *ntxd = ds.h_ck_totals[0];
+    memcpy(totals, ds.h_ck_totals, 4 * sizeof(uint32_t));
+    return RXG_OK;
+}
+
 int rxg_delivery_moved(rxg_ctx *c, const rxg_delivery *d, uint32_t *moved) {
     if (!c || !d || !moved) return RXG_EINVAL;
     *moved = 0;
@@ -2119,6 +2240,16 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
             HIPCHK(hipMemsetAsync(c->d_ddos_state, 0, sizeof(rxg_ddos_state), c->stream));
         }
     }
+    const bool cookie = (c->deliver_flags & RXG_DLV_SYNCOOKIE) != 0;
+    if (cookie) {
+        if (!c->d_ck_status) HIPCHK(hipMalloc(&c->d_ck_status, c->max_pkts));
+        if (!c->d_ck_txd) HIPCHK(hipMalloc(&c->d_ck_txd, (size_t)c->max_pkts * sizeof(rxg_txd)));
+        if (!c->d_ck_totals) HIPCHK(hipMalloc(&c->d_ck_totals, 4 * sizeof(uint32_t)));
+        if (!ds.h_ck_status) HIPCHK(hipHostMalloc((void **)&ds.h_ck_status, c->max_pkts, 0));
+        if (!ds.h_ck_txd)
+            HIPCHK(hipHostMalloc((void **)&ds.h_ck_txd, (size_t)c->max_pkts * sizeof(rxg_txd), 0));
+        if (!ds.h_ck_totals) HIPCHK(hipHostMalloc((void **)&ds.h_ck_totals, 4 * sizeof(uint32_t), 0));
+    }
     for (hipEvent_t &e : ds.tev)
         if (!e) HIPCHK(hipEventCreate(&e));
     // the TCP payloads of this burst: a free pooled buffer (a hold the caller
@@ -2153,7 +2284,7 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
         d->udp_payload = ds.h_cp_payload;
         memset(ds.h_cp_first, 0, (nf + 1) * sizeof(uint32_t));
     }
-    ds.on = ds.udp = ds.tcp = ds.gro = ds.order = ds.ddos = ds.assemble = false;
+    ds.on = ds.udp = ds.tcp = ds.gro = ds.order = ds.ddos = ds.assemble = ds.cookie = false;
     ds.nrun = ds.moved = ds.nstream = 0;
     ds.ticket = 0;
     ds.t0 = t0;
@@ -2215,6 +2346,15 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
             HIPCHK(hipMemcpyAsync(ds.h_ddos, c->d_ddos_sum, sizeof(rxg_ddos_summary),
                                   hipMemcpyDeviceToHost, c->stream));
         }
+        // SYN cookies (RXG_DLV_SYNCOOKIE): K7 reads the verdicts and the
+        // candidates' heads; its status bytes, an upper-bound copy of n
+        // descriptors and its totals go back with the other results
+        if (cookie) {
+            if ((rc = syncookie_impl(c, sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, sl.d_out,
+                                     (const uint32_t *)c->d_ck_mask, c->ck_id_space, &c->ck_p,
+                                     c->d_ck_status, c->d_ck_txd, c->d_ck_totals, c->stream)))
+                return rc;
+        }
         HIPCHK(hipEventRecord(ds.tev[3], c->stream)); // after K3 / K4
         // every result in one round trip: the counts with upper-bound copies of
         // the records (n of each) and payloads (the staged span bounds the sum of
@@ -2248,6 +2388,14 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
                 HIPCHK(hipMemcpyAsync(const_cast<uint8_t *>(d->tcp_payload), c->d_ss_payload, pos,
                                       hipMemcpyDeviceToHost, c->stream));
         }
+        if (cookie) {
+            HIPCHK(hipMemcpyAsync(ds.h_ck_totals, c->d_ck_totals, 4 * sizeof(uint32_t),
+                                  hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(ds.h_ck_status, c->d_ck_status, n, hipMemcpyDeviceToHost, c->stream));
+            if (c->ck_id_space) // (no listener id: no descriptor)
+                HIPCHK(hipMemcpyAsync(ds.h_ck_txd, c->d_ck_txd, (size_t)n * sizeof(rxg_txd),
+                                      hipMemcpyDeviceToHost, c->stream));
+        }
         HIPCHK(hipEventRecord(ds.tev[4], c->stream)); // after the results' copy out
         return RXG_OK;
     };
@@ -2264,6 +2412,7 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
     ds.order = tcp && order;
     ds.assemble = tcp && assemble;
     ds.ddos = ddos;
+    ds.cookie = cookie;
     ds.ticket = t;
     ds.t1 = t1;
     return RXG_OK;

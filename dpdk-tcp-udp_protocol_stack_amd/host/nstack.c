@@ -401,11 +401,124 @@ static void ddos_host_burst(rxg_mbuf *const *m, uint32_t n) {
     }
     free(pk), free(off), free(len);
 }
+/* SYN cookies (nstack_set_syncookies; the rule: rxgpu.h, "SYN cookies"): a
+ * listener keeps no state for a SYN.  Each burst is judged once (K7 with
+ * RXG_DLV_SYNCOOKIE on the device paths, rxg_syncookie_host in nstack_deliver):
+ * a SYN's descriptor waits in s_ck_tx for the next nstack_tx_burst, a
+ * handshake ACK whose cookie verifies creates its tcb ESTABLISHED when it
+ * reaches the LISTEN handler, any other ACK is counted.  A frame whose burst
+ * result cannot be used (verdicts of an older snapshot, a lookup made again on
+ * the live list that found another block, the option switched on between a
+ * submit and its delivery) is judged alone, by the same host call.  g_ck_mode:
+ * 0 off, 1 on, 2 on while the flood detector's alarm is up (as it stood before
+ * the burst).  All of it under g_lock. */
+#define CK_JUDGE 0xFFu         /* no burst status for this frame */
+#define CK_TX_MAX (1u << 16)   /* SYN-ACKs waiting for a TX burst; a SYN past it goes unanswered */
+static int g_ck_mode;
+static rxg_ck_params g_ck_p;
+static uint32_t g_ck_pin = 0xFFFFFFFFu; /* nstack_syncookie_tick (all ones: the clock) */
+static uint64_t g_ck_syn, g_ck_acc, g_ck_rej; /* nstack_syncookie_stats */
+static uint32_t *s_ck_mask;    /* one bit per tcb id: the listeners */
+static uint32_t s_ck_mask_cap, g_ck_space;
+static rxg_txd *s_ck_tx;       /* the waiting SYN-ACKs: [g_ck_tx_head, g_ck_tx_n) */
+static uint32_t s_ck_tx_cap, g_ck_tx_head, g_ck_tx_n;
+static int g_ck_on;            /* the burst being delivered is judged */
+static const uint8_t *g_ck_st; /* its per-frame statuses; NULL: frame by frame */
+static uint8_t g_ck_cur;       /* the status of the frame in tcp_dispatch */
+static uint8_t *s_ck_hst;      /* the host path's statuses, descriptors and frame heads */
+static rxg_txd *s_ck_htx;
+static uint8_t *s_ck_hpk;
+static uint32_t *s_ck_hoff;
+static uint16_t *s_ck_hlen;
+static uint32_t s_ck_hcap;
+
+static int ck_active(void) {
+    return g_ck_mode == 1 || (g_ck_mode == 2 && g_ddos && g_ddos_acc.alarm);
+}
+static uint32_t ck_now(void) {
+    if (g_ck_pin != 0xFFFFFFFFu) return g_ck_pin;
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return (uint32_t)((uint64_t)ts.tv_sec / 64u);
+}
+/* k descriptors behind the waiting ones (what does not fit is dropped) */
+static void ck_tx_push(const rxg_txd *d, uint32_t k) {
+    if (g_ck_tx_head == g_ck_tx_n) g_ck_tx_head = g_ck_tx_n = 0;
+    const uint32_t have = g_ck_tx_n - g_ck_tx_head;
+    if (k > CK_TX_MAX - have) k = CK_TX_MAX - have;
+    if (!k) return;
+    if (g_ck_tx_n + k > s_ck_tx_cap) {
+        if (g_ck_tx_head) {
+            memmove(s_ck_tx, s_ck_tx + g_ck_tx_head, (size_t)have * sizeof(*d));
+            g_ck_tx_head = 0, g_ck_tx_n = have;
+        }
+        if (have + k > s_ck_tx_cap) {
+            uint32_t cap = s_ck_tx_cap ? s_ck_tx_cap : 256;
+            while (cap < have + k) cap *= 2;
+            rxg_txd *t = realloc(s_ck_tx, (size_t)cap * sizeof(*t));
+            if (!t) return;
+            s_ck_tx = t, s_ck_tx_cap = cap;
+        }
+    }
+    memcpy(s_ck_tx + g_ck_tx_n, d, (size_t)k * sizeof(*d));
+    g_ck_tx_n += k;
+}
+/* a judged burst's descriptors and totals taken over */
+static void ck_take(const rxg_txd *txd, const uint32_t tot[4]) {
+    ck_tx_push(txd, tot[0]);
+    g_ck_syn += tot[0];
+    g_ck_rej += tot[2];
+}
+/* one frame judged alone, as a candidate: its status, a SYN's descriptor in *d */
+static uint8_t ck_judge_frame(const uint8_t *f, uint32_t cap, rxg_txd *d) {
+    uint8_t head[64] __attribute__((aligned(16)));
+    memset(head, 0, sizeof(head));
+    memcpy(head, f, cap < 64u ? cap : 64u);
+    const uint32_t off = 0, mask = 1u;
+    const uint16_t len = (uint16_t)(cap < 65535u ? cap : 65535u);
+    rxg_verdict v;
+    memset(&v, 0, sizeof(v));
+    v.cls = RXG_CLS_TCP, v.rc = RXG_RC_OK;
+    uint8_t st = 0;
+    uint32_t tot[4];
+    if (rxg_syncookie_host(head, &off, &len, 1, 4, &v, &mask, 1, &g_ck_p, &st, d, tot) != RXG_OK)
+        return 0;
+    return st;
+}
+/* a host-verdict burst through rxg_syncookie_host: the frames' first 64
+ * bytes packed at 64-B slots (the rule reads no byte past 47).  Sets g_ck_st;
+ * out of memory: the frames are judged one by one */
+static void ck_host_burst(rxg_mbuf *const *m, uint32_t n, const rxg_verdict *v) {
+    if (n > s_ck_hcap) {
+        free(s_ck_hst), free(s_ck_htx), free(s_ck_hpk), free(s_ck_hoff), free(s_ck_hlen);
+        s_ck_hst = malloc(n), s_ck_htx = malloc((size_t)n * sizeof(rxg_txd));
+        s_ck_hpk = aligned_alloc(64, (size_t)n * 64u);
+        s_ck_hoff = malloc((size_t)n * sizeof(uint32_t)), s_ck_hlen = malloc((size_t)n * sizeof(uint16_t));
+        s_ck_hcap = s_ck_hst && s_ck_htx && s_ck_hpk && s_ck_hoff && s_ck_hlen ? n : 0;
+        if (!s_ck_hcap) {
+            free(s_ck_hst), free(s_ck_htx), free(s_ck_hpk), free(s_ck_hoff), free(s_ck_hlen);
+            s_ck_hst = NULL, s_ck_htx = NULL, s_ck_hpk = NULL, s_ck_hoff = NULL, s_ck_hlen = NULL;
+            return;
+        }
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t c = m[i]->data_len < 64u ? m[i]->data_len : 64u;
+        memcpy(s_ck_hpk + (size_t)i * 64u, (const uint8_t *)m[i]->buf_addr + m[i]->data_off, c);
+        s_ck_hoff[i] = i * 4u; /* 16-B units */
+        s_ck_hlen[i] = m[i]->data_len;
+    }
+    uint32_t tot[4];
+    if (rxg_syncookie_host(s_ck_hpk, s_ck_hoff, s_ck_hlen, n, 4, v, s_ck_mask, g_ck_space, &g_ck_p,
+                           s_ck_hst, s_ck_htx, tot) != RXG_OK)
+        return;
+    ck_take(s_ck_htx, tot);
+    g_ck_st = s_ck_hst;
+}
 /* the delivery flags the options ask for (g_lock held) */
 static uint32_t dlv_flags(void) {
     return (g_inplace ? RXG_DLV_TCP_IN_PLACE : g_gro ? RXG_DLV_TCP_GRO : 0u) |
            (g_order ? RXG_DLV_TCP_ORDER : 0u) | (g_ddos ? RXG_DLV_DDOS : 0u) |
-           (g_assemble ? RXG_DLV_TCP_ASSEMBLE : 0u);
+           (g_assemble ? RXG_DLV_TCP_ASSEMBLE : 0u) | (g_ck_mode ? RXG_DLV_SYNCOOKIE : 0u);
 }
 static void (*g_mb_release)(rxg_mbuf *m, void *arg);
 static void *g_mb_arg;
@@ -940,6 +1053,35 @@ static void restate_tcb(struct tcp_stream *s, int lookup_moves) {
     if (lookup_moves) g_snap_gen++;
     g_dirty = 1;
 }
+/* SYN cookies: the listeners' ids as a bit mask, here and in the library
+ * (uploaded ahead of the next submit); after nlisten, the close of a listener
+ * and nstack_set_syncookies (g_lock held) */
+static int ck_sync_listeners(void) {
+    if (!g_ck_mode || !g_ctx) return RXG_OK;
+    uint32_t nl = 0, space = 0;
+    for (struct tcp_stream *s = g_tcb_set; s; s = s->next)
+        if (s->status == TCP_STATUS_LISTEN) {
+            nl++;
+            if (s->flow_id >= space) space = s->flow_id + 1u;
+        }
+    uint32_t *ids = malloc((size_t)(nl ? nl : 1) * sizeof(*ids));
+    const uint32_t words = (space + 31u) / 32u;
+    if (!ids || grow((void **)&s_ck_mask, &s_ck_mask_cap, words ? words : 1, sizeof(uint32_t))) {
+        free(ids);
+        return RXG_ENOMEM;
+    }
+    memset(s_ck_mask, 0, (size_t)(words ? words : 1) * sizeof(uint32_t));
+    nl = 0;
+    for (struct tcp_stream *s = g_tcb_set; s; s = s->next)
+        if (s->status == TCP_STATUS_LISTEN) {
+            ids[nl++] = s->flow_id;
+            s_ck_mask[s->flow_id >> 5] |= 1u << (s->flow_id & 31u);
+        }
+    g_ck_space = space;
+    const int rc = rxg_syncookie_set(g_ctx, &g_ck_p, ids, nl);
+    free(ids);
+    return rc;
+}
 
 /* the GPU TX encoder's state (defined with nstack_tx_burst) */
 static int g_tx_encode;
@@ -963,6 +1105,10 @@ int nstack_init(int device, uint32_t max_burst, uint64_t max_bytes) {
         if (rc == RXG_OK && g_ddos) {
             rxg_tune_deliver(g_ctx, dlv_flags());
             rxg_tune_ddos_thresh(g_ctx, g_ddos_thresh);
+        }
+        if (rc == RXG_OK && g_ck_mode) {
+            rxg_tune_deliver(g_ctx, dlv_flags());
+            (void)ck_sync_listeners();
         }
         /* a new context: its delivery sets start again at set 0 */
         for (uint32_t j = 0; j < RXG_DELIVER_DEPTH; j++) g_set_ref[j] = -1;
@@ -1039,6 +1185,16 @@ void nstack_fini(void) {
     g_ddos_thresh = RXG_DDOS_DEFAULT_THRESH;
     memset(&g_ddos_state, 0, sizeof(g_ddos_state));
     memset(&g_ddos_acc, 0, sizeof(g_ddos_acc));
+    g_ck_mode = 0;
+    g_ck_pin = 0xFFFFFFFFu;
+    memset(&g_ck_p, 0, sizeof(g_ck_p));
+    g_ck_syn = g_ck_acc = g_ck_rej = 0;
+    free(s_ck_mask), free(s_ck_tx), free(s_ck_hst), free(s_ck_htx), free(s_ck_hpk), free(s_ck_hoff);
+    free(s_ck_hlen);
+    s_ck_mask = NULL, s_ck_tx = NULL, s_ck_hst = NULL, s_ck_htx = NULL, s_ck_hpk = NULL;
+    s_ck_hoff = NULL, s_ck_hlen = NULL;
+    s_ck_mask_cap = g_ck_space = s_ck_tx_cap = g_ck_tx_head = g_ck_tx_n = s_ck_hcap = 0;
+    g_ck_on = 0, g_ck_st = NULL;
     g_tx_encode = 0;
     atomic_store_explicit(&g_txe_frames, 0, memory_order_relaxed);
     g_tx_mss = 0;
@@ -1160,6 +1316,7 @@ int nlisten(int sockfd, int backlog) { /* :373-386 */
         if (s->protocol == IPPROTO_TCP) {
             s->status = TCP_STATUS_LISTEN;
             restate_tcb(s, 1);
+            (void)ck_sync_listeners();
         }
         rc = 0;
     }
@@ -1464,6 +1621,7 @@ int nclose(int fd) { /* :609-666 */
             LL_REMOVE(s, g_tcb_set);
             fd_del(fd, s);
             tcb_kill(s);
+            (void)ck_sync_listeners();
             /* the reference leaves the listener's fd set in the bitmap here */
         }
     }
@@ -1647,12 +1805,39 @@ static void tcp_dispatch_assembled(struct tcp_stream *s, const uint8_t *f, uint3
 }
 
 /* tcp_process after the lookup (tcp.c:373-415) for the frame's tcb (g_lock held) */
+static void tcp_dispatch(struct tcp_stream *s, const uint8_t *f, uint32_t cap);
 static void tcp_dispatch(struct tcp_stream *s, const uint8_t *f, uint32_t cap) {
     const uint8_t fl = cap > 47 ? f[47] : 0;
     const uint16_t sport = cap >= 36 ? rd16(f + 34) : 0, dport = cap >= 38 ? rd16(f + 36) : 0;
     const uint32_t seq = cap >= 42 ? rdbe32(f + 38) : 0, ack = cap >= 46 ? rdbe32(f + 42) : 0;
     switch (s->status) {
     case TCP_STATUS_LISTEN: /* tcp_handle_listen, tcp.c:43-87 */
+        if (g_ck_on) { /* SYN cookies: no tcb from any SYN; one from a verified ACK */
+            uint8_t st = g_ck_cur;
+            g_ck_cur = 0; /* (the frame dispatched again below is not a listener's) */
+            if (st == CK_JUDGE) {
+                rxg_txd d;
+                st = ck_judge_frame(f, cap, &d);
+                if (st == RXG_CK_SYN) ck_tx_push(&d, 1), g_ck_syn++;
+                if (st == RXG_CK_ACK_BAD) g_ck_rej++;
+            }
+            if (st != RXG_CK_ACK_OK) break;
+            struct tcp_stream *c = tcb_new(rd32(f + 26), rd32(f + 30), sport, dport, TCP_STATUS_ESTABLISHED);
+            if (!c) return;
+            c->rcv_nxt = seq, c->snd_nxt = ack; /* (the client's isn + 1, the cookie + 1) */
+            if (reg_tcb(c)) {
+                ring_free(c->rcvbuf);
+                ring_free(c->sndbuf);
+                free(c);
+                return;
+            }
+            LL_ADD(c, g_tcb_set);
+            g_burst_mutated = 1;
+            g_ck_acc++;
+            wake_acceptors(c->dport);
+            tcp_dispatch(c, f, cap); /* piggybacked data or a FIN: the ESTABLISHED path */
+            break;
+        }
         if (fl & TCP_SYN) {
             struct tcp_stream *syn = tcb_new(cap >= 30 ? rd32(f + 26) : 0, cap >= 34 ? rd32(f + 30) : 0,
                                              sport, dport, TCP_STATUS_LISTEN);
@@ -1723,7 +1908,7 @@ static void tcp_dispatch(struct tcp_stream *s, const uint8_t *f, uint32_t cap) {
  * a tcb, an ACK in LAST_ACK freed one), later segments are looked up again on
  * the live list, as the reference's frame-by-frame loop would.  Returns the
  * reference's rc for the frame. */
-static int deliver_tcp(const rxg_mbuf *m, const rxg_verdict *v) {
+static int deliver_tcp(const rxg_mbuf *m, const rxg_verdict *v, uint8_t ckst) {
     if (v->rc == RXG_RC_TCP_BAD_CKSUM) return v->rc; /* depends on the bytes only */
     const uint8_t *f = (const uint8_t *)m->buf_addr + m->data_off;
     const uint32_t cap = m->data_len;
@@ -1735,6 +1920,11 @@ static int deliver_tcp(const rxg_mbuf *m, const rxg_verdict *v) {
         s = (v->rc == RXG_RC_OK && v->flow_id < s_tcb_cap) ? s_tcb_cb[v->flow_id] : NULL;
     if (!s) return RXG_RC_TCP_NO_TCB;
     g_stat[2]++;
+    /* the burst's status holds for the block the verdict named */
+    g_ck_cur = ckst != CK_JUDGE && v->rc == RXG_RC_OK && v->flow_id < s_tcb_cap &&
+                       s_tcb_cb[v->flow_id] == s
+                   ? ckst
+                   : CK_JUDGE;
     tcp_dispatch(s, f, cap);
     return RXG_RC_OK;
 }
@@ -1835,7 +2025,7 @@ static int deliver_burst(rxg_mbuf *const *m, uint32_t n, const rxg_verdict *v, i
         int rc = v[i].rc;
         if (v[i].cls == RXG_CLS_ARP) arp_learn(m[i]);
         if (v[i].cls == RXG_CLS_TCP)
-            rc = deliver_tcp(m[i], &v[i]);
+            rc = deliver_tcp(m[i], &v[i], g_ck_st ? g_ck_st[i] : CK_JUDGE);
         else
             delivered += deliver_one(m[i], &v[i], &rc);
         if (rc_out) rc_out[i] = rc;
@@ -1924,6 +2114,12 @@ int nstack_deliver(rxg_mbuf *const *m, uint32_t n, const rxg_verdict *v, uint64_
     if (rc == RXG_OK) {
         g_burst_stale = gen != g_snap_gen; /* classified against other lists */
         g_burst_mutated = 0;
+        g_ck_on = ck_active(); /* (the alarm as it stood before this burst) */
+        g_ck_st = NULL;
+        if (g_ck_on) {
+            g_ck_p.t = ck_now();
+            if (!g_burst_stale && n) ck_host_burst(m, n, v);
+        }
         if (g_ddos && n) ddos_host_burst(m, n); /* (sees the frames; changes nothing below) */
         const uint8_t *done = NULL;
         rxg_dgram *dg = NULL;
@@ -2001,6 +2197,7 @@ int nstack_deliver(rxg_mbuf *const *m, uint32_t n, const rxg_verdict *v, uint64_
         }
         delivered += deliver_burst(m, n, v, rc_out, done);
         g_udp_done = 0;
+        g_ck_on = 0, g_ck_st = NULL;
         atomic_fetch_add_explicit(&g_deliveries, 1, memory_order_release);
     }
     pthread_mutex_unlock(&g_lock);
@@ -2630,6 +2827,21 @@ static int deliver_part(rxg_mbuf *const *m, uint32_t k, const rxg_verdict *v, ui
     if (d->nseg && g_gro && rxg_delivery_runs(g_ctx, d, &run, &nrun) != RXG_OK) run = NULL, nrun = 0;
     uint32_t moved = 0; /* (ordering on at the submit: the records that moved) */
     if (d->nseg && (g_order || g_assemble) && rxg_delivery_moved(g_ctx, d, &moved) == RXG_OK) g_order_moved += moved;
+    /* SYN cookies on (the alarm as it stood before this burst): the burst's
+     * statuses, descriptors and totals when K7 ran at the submit and the
+     * verdicts' ids still name the live blocks */
+    g_ck_on = ck_active();
+    g_ck_st = NULL;
+    if (g_ck_on) {
+        const rxg_txd *ctxd = NULL;
+        uint32_t cn = 0, ctot[4];
+        g_ck_p.t = ck_now();
+        if (!g_burst_stale && rxg_delivery_cookies(g_ctx, d, &g_ck_st, &ctxd, &cn, ctot) == RXG_OK &&
+            g_ck_st)
+            ck_take(ctxd, ctot);
+        else
+            g_ck_st = NULL;
+    }
     rxg_ddos_summary dsum; /* (the detector on at the submit: the burst's summary) */
     if (g_ddos && rxg_delivery_ddos(g_ctx, d, &dsum) == RXG_OK) ddos_account(&dsum);
     struct asm_view av = {NULL, 0}; /* (assembly on at the submit: the burst's streams) */
@@ -2641,6 +2853,7 @@ static int deliver_part(rxg_mbuf *const *m, uint32_t k, const rxg_verdict *v, ui
     delivered += deliver_burst(m, k, v, rco, handled);
     g_udp_done = 0;
     g_burst_stale = 0;
+    g_ck_on = 0, g_ck_st = NULL;
     const double t4 = mono_ms();
     ph[0] += t2 - t1, ph[1] += t3 - t2, ph[2] += t4 - t3;
     return delivered;
@@ -2681,6 +2894,7 @@ int nstack_rx_burst(rxg_mbuf *const *m, uint32_t n, int *rc_out, rxg_verdict *v_
     int sub[2] = {0, 0};
     const uint64_t gen0 = g_snap_gen;
     double lib_ms = 0;
+    if (rc == RXG_OK && g_ck_mode) (void)rxg_syncookie_tick(g_ctx, ck_now());
     /* both halves go out before the first is waited for; a second half the
      * library refused is submitted again once the first is delivered */
     for (int h = 0; rc == RXG_OK && h < parts; h++) {
@@ -2794,6 +3008,7 @@ int nstack_rx_submit(rxg_mbuf *const *m, uint32_t n, int *rc_out, rxg_verdict *v
         p->m = m, p->n = n, p->rc_out = rc_out, p->v_out = v_out;
         p->gen0 = g_snap_gen;
         p->waited = 0;
+        if (g_ck_mode) (void)rxg_syncookie_tick(g_ctx, ck_now());
         memset(p->gms, 0, sizeof(p->gms));
         const double a = mono_ms();
         rc = rxg_deliver_submit(g_ctx, m, n, p->v, &p->d);
@@ -2922,6 +3137,7 @@ int nstack_tcb_add(uint32_t sip, uint32_t dip, uint16_t sport, uint16_t dport, i
         return -1;
     }
     LL_ADD(s, g_tcb_set); /* tcp.c:52 */
+    if (status == TCP_STATUS_LISTEN) (void)ck_sync_listeners();
     wake_acceptors(dport);
     pthread_mutex_unlock(&g_lock);
     return 0;
@@ -3289,6 +3505,42 @@ int nstack_ddos_status(nstack_ddos *out) {
     if (!out) return RXG_EINVAL;
     pthread_mutex_lock(&g_lock);
     *out = g_ddos_acc;
+    pthread_mutex_unlock(&g_lock);
+    return RXG_OK;
+}
+
+int nstack_set_syncookies(int mode, const uint8_t key[16]) {
+    if (mode < 0 || mode > 2 || (mode && !key)) return RXG_EINVAL;
+    pthread_mutex_lock(&g_lock);
+    int rc = mode == 2 && !g_ddos ? RXG_EINVAL : RXG_OK; /* (mode 2 reads the detector's alarm) */
+    if (rc == RXG_OK) {
+        g_ck_mode = mode;
+        if (mode) {
+            uint64_t k[2] = {0, 0};
+            for (int i = 0; i < 16; i++) k[i >> 3] |= (uint64_t)key[i] << (8 * (i & 7));
+            g_ck_p.k0 = k[0], g_ck_p.k1 = k[1];
+            g_ck_p.max_age = RXG_CK_DEFAULT_MAX_AGE;
+            g_ck_p.window = D_TCP_INITIAL_WINDOW;
+            g_ck_p.t = ck_now();
+        }
+        if (g_ctx) rc = rxg_tune_deliver(g_ctx, dlv_flags());
+        if (rc == RXG_OK) rc = ck_sync_listeners();
+    }
+    pthread_mutex_unlock(&g_lock);
+    return rc;
+}
+
+int nstack_syncookie_tick(uint32_t t) {
+    pthread_mutex_lock(&g_lock);
+    g_ck_pin = t;
+    pthread_mutex_unlock(&g_lock);
+    return RXG_OK;
+}
+
+int nstack_syncookie_stats(uint64_t out[4]) {
+    if (!out) return RXG_EINVAL;
+    pthread_mutex_lock(&g_lock);
+    out[0] = g_ck_syn, out[1] = g_ck_acc, out[2] = g_ck_rej, out[3] = 0;
     pthread_mutex_unlock(&g_lock);
     return RXG_OK;
 }
@@ -3710,6 +3962,30 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
         pthread_mutex_unlock(&s->mutex);
         if (enc) n++;
         else tx_place(fp, fl, &pos, off, len, &n);
+    }
+    /* SYN cookies: the SYN-ACKs of the judged bursts, oldest first.  The
+     * descriptor names both MACs (the SYN's, swapped): no ARP lookup */
+    while (g_ck_tx_head < g_ck_tx_n && n < max_frames && !full) {
+        const rxg_txd *c = &s_ck_tx[g_ck_tx_head];
+        if (pos + 64u > cap_bytes) {
+            full = 1;
+            break;
+        }
+        if (enc) {
+            s_txd[nd] = *c;
+            s_txd[nd].pay_off16 = (uint32_t)(s_txpay_len >> 4);
+            pos += 64u, nd++, n++;
+        } else {
+            struct tcp_fragment g;
+            memset(&g, 0, sizeof(g));
+            g.sport = c->sport, g.dport = c->dport;
+            g.seqnum = c->seq, g.acknum = c->ack;
+            g.hdrlen_off = c->hdrlen_off, g.tcp_flags = c->tcp_flags;
+            g.windows = c->window, g.tcp_urp = c->urp;
+            uint8_t *fp = pkts + pos;
+            tx_place(fp, enc_tcp(fp, c->src_mac, c->dst_mac, c->sip, c->dip, &g), &pos, off, len, &n);
+        }
+        g_ck_tx_head++;
     }
     rxg_ctx *ctx = g_ctx;
     pthread_mutex_unlock(&g_lock);

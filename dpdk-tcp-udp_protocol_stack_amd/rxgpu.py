@@ -227,6 +227,22 @@ _tune_ddos_thresh = _sig("rxg_tune_ddos_thresh", _i32, _vp, _f64)
 _ddos_reset = _sig("rxg_ddos_reset", _i32, _vp)
 _delivery_ddos = _sig("rxg_delivery_ddos", _i32, _vp, _vp, _vp)
 DLV_DDOS = 0x10
+# SYN cookies (K7): rxg_ck_params, the per-frame status values, the flag
+CK_PARAMS_DTYPE = np.dtype([("k0", "<u8"), ("k1", "<u8"), ("t", "<u4"), ("max_age", "<u4"),
+                            ("window", "<u2"), ("_r0", "<u2"), ("_r1", "<u4")])
+assert CK_PARAMS_DTYPE.itemsize == 32
+CK_SYN, CK_ACK_OK, CK_ACK_BAD, CK_DEFAULT_MAX_AGE = 1, 2, 3, 2
+DLV_SYNCOOKIE = 0x80
+_syncookie_value = _sig("rxg_syncookie_value", _u32, _u64, _u64, _u32, _u32, _u16, _u16, _u32, _u32)
+_siphash24 = _sig("rxg_siphash24", _u64, _u64, _u64, _vp, _u64)
+_syncookie_dev = _sig("rxg_syncookie_dev", _i32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _u32, _vp,
+                      _vp, _vp, _vp, _vp)
+_syncookie_host = _sig("rxg_syncookie_host", _i32, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _u32, _vp, _vp,
+                       _vp, _vp)
+_syncookie_set = _sig("rxg_syncookie_set", _i32, _vp, _vp, _vp, _u32)
+_syncookie_tick = _sig("rxg_syncookie_tick", _i32, _vp, _u32)
+_delivery_cookies = _sig("rxg_delivery_cookies", _i32, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp),
+                         C.POINTER(_u32), _vp)
 _tune_deliver = _sig("rxg_tune_deliver", _i32, _vp, _u32)
 _tune_gro = _sig("rxg_tune_gro", _i32, _vp, _u32)
 _delivery_runs = _sig("rxg_delivery_runs", _i32, _vp, _vp, C.POINTER(_vp), C.POINTER(_u32))
@@ -332,7 +348,8 @@ EXPORTED = ["rxg_open", "rxg_close", "rxg_strerror", "rxg_last_hip_error", "rxg_
             "rxg_group_close", "rxg_group_size", "rxg_counts_allreduce", "rxg_ctx_counts_allreduce",
             "rxg_ddos_dev", "rxg_ddos_bits_dev", "rxg_ddos_window_dev", "rxg_ddos_host",
             "rxg_ddos_entropy", "rxg_tune_ddos", "rxg_tune_ddos_thresh", "rxg_ddos_reset",
-            "rxg_delivery_ddos"]
+            "rxg_delivery_ddos", "rxg_syncookie_value", "rxg_siphash24", "rxg_syncookie_dev",
+            "rxg_syncookie_host", "rxg_syncookie_set", "rxg_syncookie_tick", "rxg_delivery_cookies"]
 
 
 class RxgError(RuntimeError):
@@ -665,10 +682,51 @@ class Context:
         _check(_delivery_ddos(self._h, C.byref(d), _ptr(out)), "rxg_delivery_ddos")
         return out[0]
 
+    def syncookie_dev(self, d_pkts, d_off, d_len, n: int, off_unit_log2: int, d_v, d_lmask,
+                      id_space: int, params: np.ndarray, d_status, d_txd, d_totals, stream=None):
+        """rxg_syncookie_dev: one burst through the SYN-cookie pass (K7), async
+        on stream.  params: ck_params(); d_status (u8, n), d_txd (TXD_DTYPE
+        bytes, room for n) and d_totals (u32, 4) are device buffers"""
+        def p(x):
+            return x if (x is None or isinstance(x, int)) else x.data_ptr()
+        _check(_syncookie_dev(self._h, p(d_pkts), p(d_off), p(d_len), n, off_unit_log2, p(d_v),
+                              p(d_lmask), id_space, _ptr(params), p(d_status), p(d_txd), p(d_totals),
+                              stream), "rxg_syncookie_dev")
+
+    def syncookie_set(self, params: np.ndarray, listener_ids):
+        """rxg_syncookie_set: the parameters (ck_params()) and the listeners'
+        TCP ids of the delivery bursts (DLV_SYNCOOKIE)"""
+        ids = np.ascontiguousarray(listener_ids, np.uint32)
+        _check(_syncookie_set(self._h, _ptr(params), _ptr(ids) if len(ids) else None, len(ids)),
+               "rxg_syncookie_set")
+
+    def syncookie_tick(self, t: int):
+        """rxg_syncookie_tick: the time counter of the delivery bursts"""
+        _check(_syncookie_tick(self._h, t & 0xFFFFFFFF), "rxg_syncookie_tick")
+
+    def delivery_cookies(self, handle=None):
+        """rxg_delivery_cookies of a waited-for deliver_submit handle (needs
+        the burst's n: handle), or of the last process_mbufs_deliver: copies of
+        (status u8[n], txd TXD_DTYPE[totals[0]], totals u32[4]); (None, None,
+        zeros) with DLV_SYNCOOKIE off"""
+        d = handle[2] if handle is not None else self._last_delivery
+        n = len(handle[1]) if handle is not None else self._last_n
+        st, tx, nt = _vp(), _vp(), _u32()
+        tot = np.zeros(4, np.uint32)
+        _check(_delivery_cookies(self._h, C.byref(d), C.byref(st), C.byref(tx), C.byref(nt),
+                                 _ptr(tot)), "rxg_delivery_cookies")
+        if not st.value:
+            return None, None, tot
+        status = np.frombuffer((C.c_uint8 * n).from_address(st.value), np.uint8).copy() if n \
+            else np.zeros(0, np.uint8)
+        txd = np.frombuffer((C.c_uint8 * (48 * nt.value)).from_address(tx.value),
+                            np.uint8).copy().view(TXD_DTYPE) if nt.value else np.zeros(0, TXD_DTYPE)
+        return status, txd, tot
+
     def tune_deliver(self, flags: int):
         """rxg_tune_deliver: DLV_TCP_IN_PLACE or DLV_TCP_GRO, either with
         DLV_TCP_ORDER; or DLV_TCP_ASSEMBLE (with or without DLV_TCP_ORDER); any
-        of them with DLV_DDOS (0 = the default)"""
+        of them with DLV_DDOS and DLV_SYNCOOKIE (0 = the default)"""
         _check(_tune_deliver(self._h, flags), "rxg_tune_deliver")
 
     def tune_gro(self, window: int):
@@ -706,6 +764,7 @@ class Context:
         _check(_process_mbufs_deliver(self._h, C.cast(arr, _vp), len(mbufs), _ptr(out),
                                       C.byref(d), ms), "rxg_process_mbufs_deliver")
         self._last_delivery = d
+        self._last_n = len(mbufs)
         return self._delivery_results(out, d, ms)
 
     def _delivery_results(self, out, d, ms):
@@ -948,6 +1007,51 @@ def tcp_runs_host(seg: np.ndarray, sip: np.ndarray, window: int) -> np.ndarray:
     _check(_tcp_runs_host(seg.ctypes.data if len(seg) else None, sip.ctypes.data if len(seg) else None,
                           len(seg), window, run.ctypes.data, C.byref(nrun)), "rxg_tcp_runs_host")
     return run[:nrun.value].copy()
+
+
+def ck_params(key: bytes, t: int, max_age: int = CK_DEFAULT_MAX_AGE, window: int = 14600) -> np.ndarray:
+    """rxg_ck_params (one element) from the 16 key bytes"""
+    assert len(key) == 16
+    p = np.zeros(1, CK_PARAMS_DTYPE)
+    p["k0"], p["k1"] = int.from_bytes(key[:8], "little"), int.from_bytes(key[8:], "little")
+    p["t"], p["max_age"], p["window"] = t & 0xFFFFFFFF, max_age, window
+    return p
+
+
+def siphash24(key: bytes, msg: bytes) -> int:
+    """rxg_siphash24: SipHash-2-4 of msg under the 16 key bytes"""
+    m = np.frombuffer(msg, np.uint8) if msg else np.zeros(1, np.uint8)
+    return _siphash24(int.from_bytes(key[:8], "little"), int.from_bytes(key[8:], "little"),
+                      m.ctypes.data, len(msg))
+
+
+def syncookie_value(key: bytes, sip: int, dip: int, sport: int, dport: int, isn: int, t: int) -> int:
+    """rxg_syncookie_value (sip, dip, sport, dport raw, as loaded from the frame)"""
+    return _syncookie_value(int.from_bytes(key[:8], "little"), int.from_bytes(key[8:], "little"), sip,
+                            dip, sport, dport, isn & 0xFFFFFFFF, t & 0xFFFFFFFF)
+
+
+def syncookie_host(pkts: np.ndarray, off: np.ndarray, lens: np.ndarray, off_unit_log2: int,
+                   verdicts: np.ndarray, lmask: np.ndarray, id_space: int, params: np.ndarray,
+                   pad: int = 0, canary: int = 0):
+    """rxg_syncookie_host: one burst through the SYN-cookie pass on the CPU:
+    (status, txd, totals).  With pad, the two arrays are returned whole: n +
+    pad status bytes and n + pad descriptors, pre-filled with canary"""
+    n = len(lens)
+    pkts = np.ascontiguousarray(pkts, np.uint8)
+    off = np.ascontiguousarray(off, np.uint32)
+    lens = np.ascontiguousarray(lens, np.uint16)
+    v = np.ascontiguousarray(verdicts, VERDICT_DTYPE)
+    lm = np.ascontiguousarray(lmask, np.uint32)
+    status = np.full(n + pad, canary, np.uint8)
+    txd = np.full((n + pad) * 48, canary, np.uint8)
+    tot = np.zeros(4, np.uint32)
+    _check(_syncookie_host(pkts.ctypes.data, off.ctypes.data, lens.ctypes.data, n, off_unit_log2,
+                           v.ctypes.data, lm.ctypes.data if lm.size else None, id_space, _ptr(params),
+                           status.ctypes.data, txd.ctypes.data, tot.ctypes.data), "rxg_syncookie_host")
+    if pad:
+        return status, txd, tot
+    return status, txd.view(TXD_DTYPE)[:tot[0]].copy(), tot
 
 
 def ddos_entropy(set_bits: float, total_bits: float) -> float:
@@ -1206,7 +1310,10 @@ class NStack:
                    ("nstack_set_rx_order", _i32, [_i32]),
                    ("nstack_set_rx_assemble", _i32, [_i32]),
                    ("nstack_set_rx_ddos", _i32, [_i32, C.c_double]),
-                   ("nstack_ddos_status", _i32, [_vp])]
+                   ("nstack_ddos_status", _i32, [_vp]),
+                   ("nstack_set_syncookies", _i32, [_i32, _vp]),
+                   ("nstack_syncookie_tick", _i32, [_u32]),
+                   ("nstack_syncookie_stats", _i32, [_vp])]
             for name, res, args in sig:
                 f = getattr(lib, name)
                 f.restype, f.argtypes = res, args
@@ -1540,6 +1647,23 @@ class NStack:
         out = np.zeros(1, NSTACK_DDOS_DTYPE)
         _check(self.lib.nstack_ddos_status(out.ctypes.data), "nstack_ddos_status")
         return {k: out[0][k].item() for k in NSTACK_DDOS_DTYPE.names if not k.startswith("_")}
+
+    def set_syncookies(self, mode: int, key: bytes | None = None):
+        """nstack_set_syncookies: 0 off, 1 on, 2 on while the flood detector's
+        alarm is up; key: the 16 hash-key bytes"""
+        k = np.frombuffer(key, np.uint8).copy() if key is not None else None
+        assert k is None or k.size == 16
+        _check(self.lib.nstack_set_syncookies(mode, _ptr(k)), "nstack_set_syncookies")
+
+    def syncookie_tick(self, t: int = 0xFFFFFFFF):
+        """nstack_syncookie_tick: pin the time counter (0xFFFFFFFF: the clock)"""
+        _check(self.lib.nstack_syncookie_tick(t & 0xFFFFFFFF), "nstack_syncookie_tick")
+
+    def syncookie_stats(self) -> dict:
+        """nstack_syncookie_stats: SYNs answered, connections accepted, ACKs rejected"""
+        out = np.zeros(4, np.uint64)
+        _check(self.lib.nstack_syncookie_stats(out.ctypes.data), "nstack_syncookie_stats")
+        return {"syn_answered": int(out[0]), "accepted": int(out[1]), "rejected": int(out[2])}
 
     def tx_burst(self, max_frames: int = 256, cap_bytes: int = 1 << 20, cksum: bool = False):
         """one udp_out + tcp_out pass: the frames (bytes) it produced"""

@@ -327,6 +327,41 @@ typedef struct nstack_ddos {
 } nstack_ddos;
 int nstack_set_rx_ddos(int on, double thresh);
 int nstack_ddos_status(nstack_ddos *out);
+/* SYN cookies: listeners that keep no state for a SYN (the rule: rxgpu.h, "SYN
+ * cookies").  mode 0 (the default): off, every SYN to a listener creates a
+ * tcb in SYN_RCVD as before.  mode 1: on for every listener.  mode 2: on only
+ * while the flood detector's alarm is up (RXG_EINVAL unless nstack_set_rx_ddos
+ * is on), decided once per burst from the alarm as it stood before the burst.
+ * key: the 16 bytes of the hash key (required for mode != 0).
+ * With cookies on for a burst, a listener creates no tcb from any SYN.  A SYN
+ * that passes the rule is answered by a SYN-ACK whose sequence number is the
+ * cookie: its descriptor joins the next nstack_tx_burst (the GPU encoder's
+ * descriptor list with nstack_set_tx_encode, the host encoder otherwise; at
+ * most 65536 wait, a SYN past that goes unanswered), addressed to the SYN's
+ * source MAC with no ARP lookup and no ARP learning.  A handshake ACK whose
+ * cookie verifies creates the tcb in ESTABLISHED when it reaches the listener
+ * (rcv_nxt = its seq, snd_nxt = its ack), wakes naccept, and is then
+ * dispatched on the new tcb, so data or a FIN it carries takes the normal
+ * path.  Any other ACK to a listener is counted and ignored.  The counter is
+ * CLOCK_MONOTONIC seconds / 64 (a cookie is accepted for
+ * RXG_CK_DEFAULT_MAX_AGE counters) unless nstack_syncookie_tick pins it
+ * (0xFFFFFFFF: back to the clock).  The device paths (nstack_rx_burst, the
+ * halves, nstack_rx_submit / nstack_rx_complete) run K7 with
+ * RXG_DLV_SYNCOOKIE; the host-verdict path (nstack_deliver) runs
+ * rxg_syncookie_host; the layer keeps the listener mask current (nlisten, the
+ * close of a listener).  A frame whose burst result cannot be used (a burst
+ * whose lists changed under it, nstack_stat(5)) is judged alone by the same
+ * host call.
+ * Limit: data segments of a new connection that sit in the same burst as its
+ * handshake ACK but ahead of it, or in a burst classified before the new
+ * tcb's flow-table insert landed, match the listener, fail the cookie check
+ * and are ignored (counted as rejected); the client retransmits them.  No MSS
+ * or other option is encoded in the cookie, and no RST answers a bad ACK.
+ * nstack_syncookie_stats: {SYNs answered, connections accepted, ACKs rejected,
+ * 0}.  nstack_fini resets the option, the counter pin and the counts. */
+int nstack_set_syncookies(int mode, const uint8_t key[16]);
+int nstack_syncookie_tick(uint32_t t);
+int nstack_syncookie_stats(uint64_t out[4]);
 /* Items the application has read (fragments, datagram batches) are handed
  * back to the protocol thread and freed by its next nstack_rx_burst (while
  * that burst is on the GPU) / nstack_tx_burst / nstack_deliver call (or

@@ -800,6 +800,90 @@ int rxg_tune_ddos_thresh(rxg_ctx *ctx, double thresh);
 int rxg_ddos_reset(rxg_ctx *ctx);
 int rxg_delivery_ddos(rxg_ctx *ctx, const rxg_delivery *d, rxg_ddos_summary *summary);
 
+/* ---- SYN cookies (K7, csrc/rx_syncookie.hip; opt-in)
+ * A listener answers SYNs and checks handshake ACKs without keeping state: the
+ * SYN-ACK's sequence number is a keyed hash of the connection, and the ACK that
+ * returns it proves the handshake.  The rule, on frame bytes with this
+ * project's conventions (IHL ignored, TCP header at 34, nothing past the
+ * captured length is read):
+ *   H = SipHash-2-4(k0, k1, M), 64-bit output, M = three little-endian words:
+ *     w0 = sip | (u64)dip << 32          (raw loads of frame bytes 26-29, 30-33)
+ *     w1 = sport | dport << 16 | (u64)isn << 32   (raw loads of 34-35, 36-37;
+ *                                          isn: the client's, host order)
+ *     w2 = t                             (the 32-bit time counter)
+ *   cookie(tuple, isn, t) = ((t & 0xFF) << 24) | (H & 0xFFFFFF)
+ * Frame i is a candidate when len[i] >= 54, its verdict has cls RXG_CLS_TCP
+ * and rc RXG_RC_OK, flow_id < id_space and bit flow_id of the listener mask is
+ * set.  With fl = byte 47, seq = BE bytes 38-41, ack = BE bytes 42-45:
+ *   (fl & 0x17) == 0x02 (SYN; no ACK, RST, FIN): RXG_CK_SYN, and one descriptor:
+ *     kind RXG_TXD_TCP, dst_mac = bytes 6-11, src_mac = bytes 0-5, sip / dip and
+ *     sport / dport swapped (raw), seq = cookie(tuple, isn = seq, t),
+ *     ack = seq + 1, tcp_flags 0x12, hdrlen_off 0x50, optlen 0, window =
+ *     p.window, urp = pay_off16 = pay_len = 0;
+ *   (fl & 0x16) == 0x10 (ACK; no SYN, RST; FIN and data allowed): with
+ *     c = ack - 1, isn = seq - 1, age = ((t & 0xFF) - (c >> 24)) & 0xFF:
+ *     RXG_CK_ACK_OK iff age <= max_age and (c & 0xFFFFFF) ==
+ *     (H(tuple, isn, t - age) & 0xFFFFFF), t - age mod 2^32; else RXG_CK_ACK_BAD;
+ *   anything else, and every non-candidate: 0.
+ * Descriptors are compacted in burst order (the k-th SYN's is txd[k]); totals =
+ * {SYNs answered, ACK_OK, ACK_BAD, 0}; no descriptor at or past totals[0] and
+ * no status byte at or past n is written.  The SYN-ACK carries no options (no
+ * MSS is encoded), as every SYN-ACK of the socket layer. */
+struct rxg_txd; /* the send descriptor, defined below (TX encode) */
+typedef struct rxg_ck_params {
+    uint64_t k0, k1;   /* LE64 of key bytes 0-7 and 8-15 */
+    uint32_t t;        /* the time counter */
+    uint32_t max_age;  /* counters an ACK's cookie may be old, <= 255 */
+    uint16_t window;   /* the SYN-ACK's window field, stored as it is */
+    uint16_t _r0;
+    uint32_t _r1;
+} rxg_ck_params;       /* 32 bytes */
+#define RXG_CK_SYN 1
+#define RXG_CK_ACK_OK 2
+#define RXG_CK_ACK_BAD 3
+#define RXG_CK_DEFAULT_MAX_AGE 2u
+/* cookie(tuple, isn, t); host, pure.  rxg_siphash24 is the hash it uses, on
+ * any message (for the published known answers). */
+uint32_t rxg_syncookie_value(uint64_t k0, uint64_t k1, uint32_t sip, uint32_t dip, uint16_t sport,
+                             uint16_t dport, uint32_t isn, uint32_t t);
+uint64_t rxg_siphash24(uint64_t k0, uint64_t k1, const uint8_t *msg, uint64_t len);
+/* One burst on the device, asynchronous on `stream`.  Frames as for
+ * rxg_classify_dev (off_unit_log2 >= 4, 16-B aligned frame starts), d_v the
+ * burst's 16-B verdicts, d_lmask one bit per TCP control block id
+ * ((id_space + 31) / 32 words).  *p is read at call time.  d_status: n bytes;
+ * d_txd: room for n descriptors, 16-B aligned; d_totals: 4 words, always
+ * written.  n == 0 or id_space == 0 zeroes the totals (and the n status bytes)
+ * without a launch.  RXG_EINVAL for max_age > 255 and for NULL outputs.  Calls
+ * on one context share its workspace (grown on demand in stream order) and
+ * must be ordered by the caller. */
+int rxg_syncookie_dev(rxg_ctx *ctx, const uint8_t *d_pkts, const uint32_t *d_off, const uint16_t *d_len,
+                      uint32_t n, uint32_t off_unit_log2, const rxg_verdict *d_v,
+                      const uint32_t *d_lmask, uint32_t id_space, const rxg_ck_params *p,
+                      uint8_t *d_status, struct rxg_txd *d_txd, uint32_t *d_totals, void *stream);
+/* The same on the CPU (csrc/rx_syncookie_host.cpp): no context, no device; the
+ * path of callers without a GPU and the tests' second opinion, never a
+ * fallback the device call takes. */
+int rxg_syncookie_host(const uint8_t *pkts, const uint32_t *off, const uint16_t *len, uint32_t n,
+                       uint32_t off_unit_log2, const rxg_verdict *v, const uint32_t *lmask,
+                       uint32_t id_space, const rxg_ck_params *p, uint8_t *status, struct rxg_txd *txd,
+                       uint32_t totals[4]);
+/* RXG_DLV_SYNCOOKIE (rxg_tune_deliver, combinable with every other flag): a
+ * delivery burst also runs K7 on the context's stream behind K1, with the
+ * parameters and listeners of rxg_syncookie_set (the mask is uploaded in stream
+ * order, ahead of the next submit) and the counter of rxg_syncookie_tick.  The
+ * n status bytes, an upper-bound copy of n descriptors and the totals cross
+ * PCIe with the other results; verdicts, records and payloads are what they
+ * are without the flag.  rxg_delivery_cookies returns them for a waited-for
+ * burst, valid as long as the burst's delivery set is; NULL / 0 when the flag
+ * was off for it.  Without rxg_syncookie_set no frame is a candidate.  struct
+ * rxg_delivery is unchanged.  Off by default.  (0x40 is not a flag:
+ * rxg_tune_deliver keeps refusing it.) */
+#define RXG_DLV_SYNCOOKIE 0x80u
+int rxg_syncookie_set(rxg_ctx *ctx, const rxg_ck_params *p, const uint32_t *listener_ids, uint32_t nl);
+int rxg_syncookie_tick(rxg_ctx *ctx, uint32_t t);
+int rxg_delivery_cookies(rxg_ctx *ctx, const rxg_delivery *d, const uint8_t **status,
+                         const struct rxg_txd **txd, uint32_t *ntxd, uint32_t totals[4]);
+
 /* TX checksum generation (the send side's per-frame work, udp.c:84-95 and
  * tcp.c:444-463): for every IPv4 frame of the burst, the IPv4 header checksum
  * (rte_ipv4_cksum, rte_ip.h:255-265) is written at frame offset 24, and for
