@@ -1836,65 +1836,11 @@ int rxg_process_mbufs_udp(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdic
     return rxg_wait(c, t);
 }
 
-static int segsort_impl(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off,
-                        const uint16_t *d_len, uint32_t n, uint32_t off_unit_log2, const uint4 *d_v,
-                        rxg_segment *d_seg, uint8_t *d_payload, uint64_t cap, uint32_t *d_totals,
-                        hipStream_t s) {
-    const size_t ws = rx_segsort_ws_bytes(n);
-    if (ws > c->d_ss_ws_cap) { // (its uses are all on s: freed and grown in stream order)
-        int rc = ensure_dev_async(&c->d_ss_ws, &c->d_ss_ws_cap, ws, s);
-        if (rc) return rc;
-    }
-    HIPCHK(rx_segsort_launch(d_pkts, d_off, d_len, n, off_unit_log2, d_v, c->fs.tcp.id_space(), d_seg,
-                             d_payload, cap, d_totals, c->d_ss_ws, s));
-    return RXG_OK;
-}
-
-// K4 with receive coalescing (rx_segsort.hip); the workspace is K4's, grown
-static int gro_impl(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off, const uint16_t *d_len,
-                    uint32_t n, uint32_t off_unit_log2, const uint4 *d_v, uint32_t W,
-                    rxg_segment *d_seg, rxg_tcp_run *d_run, uint8_t *d_payload, uint64_t cap,
-                    uint32_t *d_totals, hipStream_t s) {
-    const size_t ws = rx_gro_ws_bytes(n);
-    if (ws > c->d_ss_ws_cap) {
-        int rc = ensure_dev_async(&c->d_ss_ws, &c->d_ss_ws_cap, ws, s);
-        if (rc) return rc;
-    }
-    HIPCHK(rx_gro_launch(d_pkts, d_off, d_len, n, off_unit_log2, d_v, c->fs.tcp.id_space(), W, d_seg,
-                         d_run, d_payload, cap, d_totals, c->d_ss_ws, s));
-    return RXG_OK;
-}
-
-// K4 or its coalescing form (W != 0) on the sequence-ordered segments
-// (rx_segsort.hip); the workspace is K4's, grown
-static int order_impl(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off, const uint16_t *d_len,
-                      uint32_t n, uint32_t off_unit_log2, const uint4 *d_v, uint32_t W,
-                      rxg_segment *d_seg, rxg_tcp_run *d_run, uint8_t *d_payload, uint64_t cap,
-                      uint32_t *d_totals, hipStream_t s) {
-    const size_t ws = rx_order_ws_bytes(n);
-    if (ws > c->d_ss_ws_cap) {
-        int rc = ensure_dev_async(&c->d_ss_ws, &c->d_ss_ws_cap, ws, s);
-        if (rc) return rc;
-    }
-    HIPCHK(rx_order_launch(d_pkts, d_off, d_len, n, off_unit_log2, d_v, c->fs.tcp.id_space(), W,
-                           d_seg, d_run, d_payload, cap, d_totals, c->d_ss_ws, s));
-    return RXG_OK;
-}
-
-// the sort, the ordering stage and the stream assembly (rx_segsort.hip); the
-// workspace is K4's, grown
-static int assemble_impl(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off,
-                         const uint16_t *d_len, uint32_t n, uint32_t off_unit_log2, const uint4 *d_v,
-                         rxg_segment *d_seg, rxg_tcp_stream *d_stream, uint8_t *d_payload,
-                         uint64_t cap, uint32_t *d_totals, hipStream_t s) {
-    const size_t ws = rx_assemble_ws_bytes(n);
-    if (ws > c->d_ss_ws_cap) {
-        int rc = ensure_dev_async(&c->d_ss_ws, &c->d_ss_ws_cap, ws, s);
-        if (rc) return rc;
-    }
-    HIPCHK(rx_assemble_launch(d_pkts, d_off, d_len, n, off_unit_log2, d_v, c->fs.tcp.id_space(), d_seg,
-                              d_stream, d_payload, cap, d_totals, c->d_ss_ws, s));
-    return RXG_OK;
+// K4's workspace (rx_segsort.hip: one buffer for all four forms) grown to
+// bytes; its uses are all on s, so it is freed and grown in stream order
+static int k4_ws_grow(rxg_ctx *c, size_t bytes, hipStream_t s) {
+    if (bytes <= c->d_ss_ws_cap) return RXG_OK;
+    return ensure_dev_async(&c->d_ss_ws, &c->d_ss_ws_cap, bytes, s);
 }
 
 int rxg_payload_hold(rxg_ctx *c, int32_t ref) {
@@ -1919,8 +1865,12 @@ int rxg_tcp_compact_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off
         return RXG_EINVAL; // (d_payload null: records only, RXG_DLV_TCP_IN_PLACE)
     if (off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
     DEVGUARD(c);
-    return segsort_impl(c, d_pkts, d_off, d_len, n, off_unit_log2, reinterpret_cast<const uint4 *>(d_v),
-                        d_seg, d_payload, payload_cap, d_totals, (hipStream_t)stream);
+    const int rc = k4_ws_grow(c, rx_segsort_ws_bytes(n), (hipStream_t)stream);
+    if (rc) return rc;
+    HIPCHK(rx_segsort_launch(d_pkts, d_off, d_len, n, off_unit_log2, reinterpret_cast<const uint4 *>(d_v),
+                             c->fs.tcp.id_space(), d_seg, d_payload, payload_cap, d_totals, c->d_ss_ws,
+                             (hipStream_t)stream));
+    return RXG_OK;
 }
 
 int rxg_tcp_coalesce_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off,
@@ -1934,8 +1884,12 @@ int rxg_tcp_coalesce_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_of
     if (W < 1u || W > RXG_GRO_MAX_WINDOW) return RXG_EINVAL;
     if (off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
     DEVGUARD(c);
-    return gro_impl(c, d_pkts, d_off, d_len, n, off_unit_log2, reinterpret_cast<const uint4 *>(d_v), W,
-                    d_seg, d_run, d_payload, payload_cap, d_totals, (hipStream_t)stream);
+    const int rc = k4_ws_grow(c, rx_gro_ws_bytes(n), (hipStream_t)stream);
+    if (rc) return rc;
+    HIPCHK(rx_gro_launch(d_pkts, d_off, d_len, n, off_unit_log2, reinterpret_cast<const uint4 *>(d_v),
+                         c->fs.tcp.id_space(), W, d_seg, d_run, d_payload, payload_cap, d_totals,
+                         c->d_ss_ws, (hipStream_t)stream));
+    return RXG_OK;
 }
 
 int rxg_tcp_compact_ordered_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off,
@@ -1950,8 +1904,12 @@ int rxg_tcp_compact_ordered_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_
     if (W > RXG_GRO_MAX_WINDOW || (W && (!d_payload || (n && !d_run)))) return RXG_EINVAL;
     if (off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
     DEVGUARD(c);
-    return order_impl(c, d_pkts, d_off, d_len, n, off_unit_log2, reinterpret_cast<const uint4 *>(d_v),
-                      W, d_seg, d_run, d_payload, payload_cap, d_totals, (hipStream_t)stream);
+    const int rc = k4_ws_grow(c, rx_order_ws_bytes(n), (hipStream_t)stream);
+    if (rc) return rc;
+    HIPCHK(rx_order_launch(d_pkts, d_off, d_len, n, off_unit_log2, reinterpret_cast<const uint4 *>(d_v),
+                           c->fs.tcp.id_space(), W, d_seg, d_run, d_payload, payload_cap, d_totals,
+                           c->d_ss_ws, (hipStream_t)stream));
+    return RXG_OK;
 }
 
 // the detector's three launches on s; the context's workspace is grown first
@@ -2043,9 +2001,12 @@ int rxg_tcp_assemble_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_of
     if (n && (!d_pkts || !d_off || !d_len || !d_v || !d_seg || !d_stream)) return RXG_EINVAL;
     if (off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
     DEVGUARD(c);
-    return assemble_impl(c, d_pkts, d_off, d_len, n, off_unit_log2,
-                         reinterpret_cast<const uint4 *>(d_v), d_seg, d_stream, d_payload,
-                         payload_cap, d_totals, (hipStream_t)stream);
+    const int rc = k4_ws_grow(c, rx_assemble_ws_bytes(n), (hipStream_t)stream);
+    if (rc) return rc;
+    HIPCHK(rx_assemble_launch(d_pkts, d_off, d_len, n, off_unit_log2, reinterpret_cast<const uint4 *>(d_v),
+                              c->fs.tcp.id_space(), d_seg, d_stream, d_payload, payload_cap, d_totals,
+                              c->d_ss_ws, (hipStream_t)stream));
+    return RXG_OK;
 }
 
 int rxg_delivery_streams(rxg_ctx *c, const rxg_delivery *d, const rxg_tcp_stream **stream,
@@ -2313,27 +2274,30 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
                                    c->stream)))
                 return rc;
         tcp = c->fs.tcp.id_space() > 0;
-        if (tcp && assemble) {
-            if ((rc = assemble_impl(c, sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, sl.d_out, c->d_ss_seg,
-                                    c->d_ss_stream, c->d_ss_payload, c->max_bytes, c->d_ss_totals,
-                                    c->stream)))
-                return rc;
-        } else if (tcp && order) {
-            if ((rc = order_impl(c, sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, sl.d_out,
-                                 gro ? c->gro_window : 0u, c->d_ss_seg, c->d_ss_run,
-                                 inplace ? nullptr : c->d_ss_payload, c->max_bytes, c->d_ss_totals,
-                                 c->stream)))
-                return rc;
-        } else if (tcp && gro) {
-            if ((rc = gro_impl(c, sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, sl.d_out, c->gro_window,
-                               c->d_ss_seg, c->d_ss_run, c->d_ss_payload, c->max_bytes,
-                               c->d_ss_totals, c->stream)))
-                return rc;
-        } else if (tcp) {
-            if ((rc = segsort_impl(c, sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, sl.d_out, c->d_ss_seg,
-                                   inplace ? nullptr : c->d_ss_payload, c->max_bytes,
-                                   c->d_ss_totals, c->stream)))
-                return rc;
+        if (tcp) {
+            const uint32_t nt = c->fs.tcp.id_space();
+            const size_t ws = assemble ? rx_assemble_ws_bytes(n)
+                              : order  ? rx_order_ws_bytes(n)
+                              : gro    ? rx_gro_ws_bytes(n)
+                                       : rx_segsort_ws_bytes(n);
+            if ((rc = k4_ws_grow(c, ws, c->stream))) return rc;
+            if (assemble)
+                HIPCHK(rx_assemble_launch(sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, sl.d_out, nt,
+                                          c->d_ss_seg, c->d_ss_stream, c->d_ss_payload, c->max_bytes,
+                                          c->d_ss_totals, c->d_ss_ws, c->stream));
+            else if (order)
+                HIPCHK(rx_order_launch(sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, sl.d_out, nt,
+                                       gro ? c->gro_window : 0u, c->d_ss_seg, c->d_ss_run,
+                                       inplace ? nullptr : c->d_ss_payload, c->max_bytes,
+                                       c->d_ss_totals, c->d_ss_ws, c->stream));
+            else if (gro)
+                HIPCHK(rx_gro_launch(sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, sl.d_out, nt,
+                                     c->gro_window, c->d_ss_seg, c->d_ss_run, c->d_ss_payload,
+                                     c->max_bytes, c->d_ss_totals, c->d_ss_ws, c->stream));
+            else
+                HIPCHK(rx_segsort_launch(sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, sl.d_out, nt,
+                                         c->d_ss_seg, inplace ? nullptr : c->d_ss_payload, c->max_bytes,
+                                         c->d_ss_totals, c->d_ss_ws, c->stream));
         }
         // the flood detector (RXG_DLV_DDOS) reads the staged frames once more;
         // bursts follow each other on the stream, so the window follows

@@ -19,7 +19,16 @@
 //      contiguous slice: one allocation and one copy per connection per
 //      burst on the host (host/nstack.c).
 // Bytes past a frame's capture read as 0 (the delivery oracle's rule).
+//
+// Three more forms share the sort: receive coalescing, sequence ordering and
+// stream assembly (their sections below).  The device pieces they share with
+// K4 stand with K4's kernels; the host side, at the end of the file, is one
+// workspace description and five stages (sort, order, record, coalesce,
+// assemble) that the four rx_*_launch entry points compose.
 #include <hip/hip_runtime.h>
+
+#include <initializer_list>
+#include <type_traits>
 
 #include "rx_common.h"
 
@@ -40,6 +49,159 @@ __device__ __forceinline__ uint32_t ss_wave_scan(uint32_t x) {
     x += __builtin_amdgcn_update_dpp(0u, x, 0x142, 0xA, 0xF, false);
     x += __builtin_amdgcn_update_dpp(0u, x, 0x143, 0xC, 0xF, false);
     return x;
+}
+
+// ss_wave_scan with max for +: the lanes shifted in read 0, the identity of
+// max on unsigned values as well
+__device__ __forceinline__ uint32_t ss_wave_max(uint32_t x) {
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x111, 0xF, 0xF, true));
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x112, 0xF, 0xF, true));
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x114, 0xF, 0xF, true));
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x118, 0xF, 0xF, true));
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x142, 0xA, 0xF, false));
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x143, 0xC, 0xF, false));
+    return x;
+}
+
+// inclusive scan (sum or max) over the block's SS_THREADS values, every
+// thread calling; ws: SS_THREADS / 64 words of LDS of this scan's own;
+// total = the block's sum / max
+template <bool MAX>
+__device__ __forceinline__ uint32_t ss_block_scan(uint32_t x, uint32_t *ws, uint32_t &total) {
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    const uint32_t inc = MAX ? ss_wave_max(x) : ss_wave_scan(x);
+    if (lane == 63u) ws[w] = inc;
+    __syncthreads();
+    uint32_t pre = 0u, all = 0u;
+#pragma unroll
+    for (uint32_t q = 0; q < SS_THREADS / 64u; ++q) {
+        const uint32_t v = ws[q];
+        if (q < w) pre = MAX ? max(pre, v) : pre + v;
+        all = MAX ? max(all, v) : all + v;
+    }
+    total = all;
+    return MAX ? max(inc, pre) : inc + pre;
+}
+
+// what the frame of sorted segment j says, the one decode of every form: the
+// record's header fields (ncopy and offset left 0: each form's own), the
+// source address, the captured bytes past the TCP header, and "neither SYN nor
+// RST".  A byte at or past the capture reads as 0.
+struct ss_frame {
+    rxg_segment s;
+    uint32_t sip, avail, movable;
+};
+__device__ __forceinline__ ss_frame ss_decode(const uint8_t *__restrict__ pkts,
+                                              const uint32_t *__restrict__ off,
+                                              const uint16_t *__restrict__ len, uint32_t unit_log2,
+                                              const uint32_t *__restrict__ keys,
+                                              const uint32_t *__restrict__ vals, uint32_t j) {
+    ss_frame d;
+    const uint32_t i = vals[j];
+    const uint8_t *f = pkts + ((uint64_t)off[i] << unit_log2);
+    const uint32_t cap = len[i];
+    auto b = [&](uint32_t k) -> uint32_t { return k < cap ? (uint32_t)f[k] : 0u; };
+    const uint32_t tl = (b(16) << 8) | b(17); // ip total_length (tcp.c:391)
+    d.s.frame = i;
+    d.s.flow = keys[j];
+    d.s.seq = (b(38) << 24) | (b(39) << 16) | (b(40) << 8) | b(41);
+    d.s.ack = (b(42) << 24) | (b(43) << 16) | (b(44) << 8) | b(45);
+    d.s.hl = (uint8_t)(b(46) >> 4);
+    d.s.flags = (uint8_t)b(47);
+    d.s.plen = (int32_t)tl - 20 - 4 * (int32_t)d.s.hl; // tcp.c:145-146 with iTcplen = tl - 20
+    d.s.offset = 0u;
+    d.s.sport = (uint16_t)(b(34) | (b(35) << 8));
+    d.s.dport = (uint16_t)(b(36) | (b(37) << 8));
+    d.s.ncopy = 0u;
+    d.sip = b(26) | (b(27) << 8) | (b(28) << 16) | (b(29) << 24);
+    const uint32_t from = 34u + 4u * d.s.hl;
+    d.avail = cap > from ? cap - from : 0u;
+    d.movable = (d.s.flags & 0x06u) == 0u;
+    return d;
+}
+
+// the payload K4 and its coalescing form keep: PSH and plen > 0
+// (tcp.c:153-166), the captured part
+__device__ __forceinline__ uint32_t ss_keep(const ss_frame &d) {
+    return ((d.s.flags & 0x08u) && d.s.plen > 0) ? min((uint32_t)d.s.plen, d.avail) : 0u;
+}
+
+// the group-head step of a block of the ordering and assembly forms, every
+// thread calling with its decoded position (d zeroed past the delivered
+// segments): j heads a group unless it and its predecessor are movable records
+// of one connection (flow, source address, ports); the predecessors meet in
+// LDS, the block's own decoded again by thread 0.  Returns 1 + the last head
+// at or before j inside the block (0: none yet); bH[block] = the block's last
+// head, bZ[block] = 0 (the sum half of gro_scan_kernel runs beside the max
+// half, on zeros).
+__device__ __forceinline__ uint32_t ss_group_head(
+    const uint8_t *__restrict__ pkts, const uint32_t *__restrict__ off,
+    const uint16_t *__restrict__ len, uint32_t unit_log2, const uint32_t *__restrict__ keys,
+    const uint32_t *__restrict__ vals, uint32_t nseg, const ss_frame &d, uint64_t *__restrict__ bH,
+    uint64_t *__restrict__ bZ) {
+    __shared__ uint32_t pf[SS_THREADS + 1u], ps[SS_THREADS + 1u], pp[SS_THREADS + 1u],
+        pm[SS_THREADS + 1u];
+    __shared__ uint32_t ws[SS_THREADS / 64u];
+    const uint32_t t = threadIdx.x;
+    const uint32_t j0 = blockIdx.x * SS_THREADS, j = j0 + t;
+    const uint32_t ports = (uint32_t)d.s.sport | ((uint32_t)d.s.dport << 16);
+    pf[t + 1u] = d.s.flow, ps[t + 1u] = d.sip, pp[t + 1u] = ports, pm[t + 1u] = d.movable;
+    if (t == 0u) {
+        ss_frame p = {};
+        if (j0) p = ss_decode(pkts, off, len, unit_log2, keys, vals, j0 - 1u);
+        pf[0] = p.s.flow, ps[0] = p.sip, pm[0] = p.movable;
+        pp[0] = (uint32_t)p.s.sport | ((uint32_t)p.s.dport << 16);
+    }
+    __syncthreads();
+    const bool head = !j || !d.movable || !pm[t] || pf[t] != d.s.flow || ps[t] != d.sip ||
+                      pp[t] != ports;
+    uint32_t hmax;
+    const uint32_t hinc = ss_block_scan<true>((j < nseg && head) ? j + 1u : 0u, ws, hmax);
+    if (t == 0u) {
+        bH[blockIdx.x] = hmax;
+        bZ[blockIdx.x] = 0u;
+    }
+    return hinc;
+}
+
+// 16 bytes of frame f from byte a, at any phase: five dword loads below the
+// capture (a dword past it reads as 0), realigned with v_alignbyte
+__device__ __forceinline__ void ss_fetch16(const uint8_t *__restrict__ f, uint32_t fcap, uint32_t a,
+                                           uint32_t (&o4)[4]) {
+    const uint32_t a0 = a & ~3u, sh = a & 3u;
+    uint32_t wv[5];
+#pragma unroll
+    for (uint32_t q = 0; q < 5u; ++q) {
+        const uint32_t p = a0 + 4u * q;
+        wv[q] = p < fcap ? *reinterpret_cast<const uint32_t *>(f + p) : 0u;
+    }
+#pragma unroll
+    for (uint32_t q = 0; q < 4u; ++q)
+        o4[q] = sh ? __builtin_amdgcn_alignbyte(wv[q + 1], wv[q], sh) : wv[q];
+}
+
+// a wave copies count bytes of frame f from byte src to payload + o, source
+// and destination at any byte phase: the bytes up to the first 16-B boundary
+// of the destination and those after the last one as byte stores, the chunks
+// between as 16-B stores.  Every byte has one writer and no lane reads the
+// destination.
+__device__ __forceinline__ void ss_copy_bytes(const uint8_t *__restrict__ f, uint32_t fcap,
+                                              uint32_t src, uint32_t count,
+                                              uint8_t *__restrict__ payload, uint64_t o,
+                                              uint32_t lane) {
+    const uint32_t hlen = min(count, (16u - (uint32_t)(o & 15u)) & 15u);
+    const uint32_t nb = (count - hlen) >> 4, tb = hlen + 16u * nb, tlen = count - tb;
+    if (lane < hlen) payload[o + lane] = src + lane < fcap ? f[src + lane] : (uint8_t)0u;
+    if (lane >= 16u && lane - 16u < tlen) {
+        const uint32_t q = tb + (lane - 16u);
+        payload[o + q] = src + q < fcap ? f[src + q] : (uint8_t)0u;
+    }
+    for (uint32_t c = lane; c < nb; c += 64u) {
+        uint32_t o4[4];
+        ss_fetch16(f, fcap, src + hlen + 16u * c, o4);
+        *reinterpret_cast<uint4 *>(payload + o + hlen + 16u * c) =
+            make_uint4(o4[0], o4[1], o4[2], o4[3]);
+    }
 }
 
 // sort key of frame i in the first pass: its tcb id for a delivered TCP
@@ -182,23 +344,9 @@ __global__ __launch_bounds__(SS_THREADS) void ss_record_kernel(
     rxg_segment s;
     uint32_t padded = 0u;
     if (j < nseg) {
-        const uint32_t i = vals[j];
-        const uint8_t *f = pkts + ((uint64_t)off[i] << unit_log2);
-        const uint32_t cap = len[i];
-        auto b = [&](uint32_t k) -> uint32_t { return k < cap ? (uint32_t)f[k] : 0u; };
-        const uint32_t tl = (b(16) << 8) | b(17); // ip total_length (tcp.c:391)
-        s.frame = i;
-        s.flow = keys[j];
-        s.seq = (b(38) << 24) | (b(39) << 16) | (b(40) << 8) | b(41);
-        s.ack = (b(42) << 24) | (b(43) << 16) | (b(44) << 8) | b(45);
-        s.hl = (uint8_t)(b(46) >> 4);
-        s.flags = (uint8_t)b(47);
-        s.plen = (int32_t)tl - 20 - 4 * (int32_t)s.hl; // tcp.c:145-146 with iTcplen = tl - 20
-        s.sport = (uint16_t)(b(34) | (b(35) << 8));
-        s.dport = (uint16_t)(b(36) | (b(37) << 8));
-        const uint32_t from = 34u + 4u * s.hl;
-        const uint32_t avail = cap > from ? cap - from : 0u;
-        const uint32_t keep = ((s.flags & 0x08u) && s.plen > 0) ? min((uint32_t)s.plen, avail) : 0u;
+        const ss_frame d = ss_decode(pkts, off, len, unit_log2, keys, vals, j);
+        const uint32_t keep = ss_keep(d);
+        s = d.s;
         s.ncopy = (uint16_t)keep;
         padded = (keep + 15u) & ~15u;
     }
@@ -245,17 +393,10 @@ __global__ __launch_bounds__(SS_THREADS) void ss_copy_kernel(
     const uint32_t fcap = len[s.frame];
     const uint32_t src = 34u + 4u * s.hl;
     for (uint32_t c = lane; 16u * c < ncopy; c += 64u) {
-        const uint32_t a = src + 16u * c, a0 = a & ~3u, sh = a & 3u;
-        uint32_t wv[5];
-#pragma unroll
-        for (uint32_t q = 0; q < 5u; ++q) {
-            const uint32_t p = a0 + 4u * q;
-            wv[q] = p < fcap ? *reinterpret_cast<const uint32_t *>(f + p) : 0u;
-        }
         uint32_t o4[4];
+        ss_fetch16(f, fcap, src + 16u * c, o4);
 #pragma unroll
-        for (uint32_t q = 0; q < 4u; ++q) {
-            o4[q] = sh ? __builtin_amdgcn_alignbyte(wv[q + 1], wv[q], sh) : wv[q];
+        for (uint32_t q = 0; q < 4u; ++q) { // the chunk's bytes at or past ncopy: 0
             const uint32_t b0 = 16u * c + 4u * q;
             const uint32_t keep = ncopy > b0 ? ncopy - b0 : 0u;
             if (keep < 4u) o4[q] &= keep ? ((1u << (8u * keep)) - 1u) : 0u;
@@ -264,72 +405,7 @@ __global__ __launch_bounds__(SS_THREADS) void ss_copy_kernel(
     }
 }
 
-inline uint32_t ss_tiles(uint32_t n) { return (uint32_t)(((uint64_t)n + SS_TILE - 1) / SS_TILE); }
-inline uint32_t ss_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + SS_THREADS - 1) / SS_THREADS); }
-inline size_t ss_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 } // namespace
-
-// workspace: keys and values twice (ping-pong), the digit histograms, the
-// record blocks' payload sizes
-size_t rx_segsort_ws_bytes(uint32_t n) {
-    const size_t nn = n ? n : 1;
-    return 4 * ss_align(nn * 4) + ss_align((size_t)SS_DIGITS * (ss_tiles(n) ? ss_tiles(n) : 1) * 4) +
-           ss_align((size_t)(ss_blocks(n) ? ss_blocks(n) : 1) * 4);
-}
-
-// d_totals: 3 (segments, payload bytes, overflow flag)
-hipError_t rx_segsort_launch(const uint8_t *pkts, const uint32_t *off, const uint16_t *len,
-                             uint32_t n, uint32_t unit_log2, const uint4 *verd, uint32_t nt,
-                             rxg_segment *seg, uint8_t *payload, uint64_t cap, uint32_t *totals,
-                             void *ws, hipStream_t s) {
-    hipError_t e = hipMemsetAsync(totals, 0, 3 * sizeof(uint32_t), s);
-    if (e != hipSuccess || n == 0 || nt == 0) return e;
-    const size_t nn = ss_align((size_t)n * 4);
-    uint8_t *w8 = static_cast<uint8_t *>(ws);
-    uint32_t *ka = reinterpret_cast<uint32_t *>(w8), *va = reinterpret_cast<uint32_t *>(w8 + nn);
-    uint32_t *kb = reinterpret_cast<uint32_t *>(w8 + 2 * nn), *vb = reinterpret_cast<uint32_t *>(w8 + 3 * nn);
-    const uint32_t ntiles = ss_tiles(n), nblk = ss_blocks(n);
-    uint32_t *hist = reinterpret_cast<uint32_t *>(w8 + 4 * nn);
-    uint32_t *tsum = reinterpret_cast<uint32_t *>(w8 + 4 * nn + ss_align((size_t)SS_DIGITS * ntiles * 4));
-    // key bits: ids 0..nt-1 and the sentinel nt
-    const uint32_t bits = 32u - (uint32_t)__builtin_clz(nt);
-    const uint32_t passes = (bits + 7u) / 8u;
-    const uint32_t *kin = nullptr, *vin = nullptr;
-    uint32_t *kout = ka, *vout = va;
-    for (uint32_t p = 0; p < passes; ++p) {
-        const uint32_t shift = 8u * p;
-        if (p == 0)
-            hipLaunchKernelGGL(ss_hist_kernel<true>, dim3(ntiles), dim3(SS_THREADS), 0, s, verd,
-                               nullptr, n, nt, shift, ntiles, hist, totals);
-        else
-            hipLaunchKernelGGL(ss_hist_kernel<false>, dim3(ntiles), dim3(SS_THREADS), 0, s, verd,
-                               kin, n, nt, shift, ntiles, hist, totals);
-        hipLaunchKernelGGL(ss_scan_kernel, dim3(1), dim3(1024), 0, s, hist, SS_DIGITS * ntiles,
-                           nullptr);
-        if (p == 0)
-            hipLaunchKernelGGL(ss_scatter_kernel<true>, dim3(ntiles), dim3(SS_THREADS), 0, s, verd,
-                               nullptr, nullptr, n, nt, shift, ntiles, hist, kout, vout);
-        else
-            hipLaunchKernelGGL(ss_scatter_kernel<false>, dim3(ntiles), dim3(SS_THREADS), 0, s, verd,
-                               kin, vin, n, nt, shift, ntiles, hist, kout, vout);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        kin = kout, vin = vout;
-        kout = (kout == ka) ? kb : ka;
-        vout = (vout == va) ? vb : va;
-    }
-    if (!payload) { // in place: records only, offset = the payload's offset in its frame
-        hipLaunchKernelGGL(ss_record_kernel<true>, dim3(nblk), dim3(SS_THREADS), 0, s, pkts, off,
-                           len, unit_log2, kin, vin, totals, seg, tsum);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(ss_record_kernel<false>, dim3(nblk), dim3(SS_THREADS), 0, s, pkts, off, len,
-                       unit_log2, kin, vin, totals, seg, tsum);
-    hipLaunchKernelGGL(ss_scan_kernel, dim3(1), dim3(1024), 0, s, tsum, nblk, totals + 1);
-    hipLaunchKernelGGL(ss_copy_kernel, dim3((uint32_t)(((uint64_t)n + 3) / 4)), dim3(SS_THREADS), 0,
-                       s, pkts, off, len, unit_log2, tsum, seg, payload, cap, totals);
-    return hipGetLastError();
-}
 
 // ---- Receive coalescing (GRO): K4 with the in-sequence trains of a
 // connection laid down as contiguous byte ranges (the rule: include/rxgpu.h,
@@ -346,38 +422,6 @@ hipError_t rx_segsort_launch(const uint8_t *pkts, const uint32_t *off, const uin
 namespace {
 
 #define GRO_HEADBIT 0x80000000u
-
-// ss_wave_scan with max for +: the lanes shifted in read 0, the identity of
-// max on unsigned values as well
-__device__ __forceinline__ uint32_t gro_wave_max(uint32_t x) {
-    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x111, 0xF, 0xF, true));
-    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x112, 0xF, 0xF, true));
-    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x114, 0xF, 0xF, true));
-    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x118, 0xF, 0xF, true));
-    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x142, 0xA, 0xF, false));
-    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0u, x, 0x143, 0xC, 0xF, false));
-    return x;
-}
-
-// inclusive scan (sum or max) over the block's SS_THREADS values, every
-// thread calling; ws: SS_THREADS / 64 words of LDS of this scan's own;
-// total = the block's sum / max
-template <bool MAX>
-__device__ __forceinline__ uint32_t gro_block_scan(uint32_t x, uint32_t *ws, uint32_t &total) {
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const uint32_t inc = MAX ? gro_wave_max(x) : ss_wave_scan(x);
-    if (lane == 63u) ws[w] = inc;
-    __syncthreads();
-    uint32_t pre = 0u, all = 0u;
-#pragma unroll
-    for (uint32_t q = 0; q < SS_THREADS / 64u; ++q) {
-        const uint32_t v = ws[q];
-        if (q < w) pre = MAX ? max(pre, v) : pre + v;
-        all = MAX ? max(all, v) : all + v;
-    }
-    total = all;
-    return MAX ? max(inc, pre) : inc + pre;
-}
 
 // exclusive scan in place of a block array of 64-bit values, one block (a
 // thread per contiguous chunk): m = the blocks of *cnt items; block 0 sums
@@ -421,36 +465,19 @@ struct gro_key {
     uint32_t flow, sip, ports, ack, seq, next_seq, merge;
 };
 
-// the record of sorted segment j, field for field ss_record_kernel's (offset
-// left 0), and its link key
+// the record of sorted segment j, K4's (offset left 0), and its link key
 __device__ __forceinline__ rxg_segment gro_decode(const uint8_t *__restrict__ pkts,
                                                   const uint32_t *__restrict__ off,
                                                   const uint16_t *__restrict__ len,
                                                   uint32_t unit_log2, const uint32_t *__restrict__ keys,
                                                   const uint32_t *__restrict__ vals, uint32_t j,
                                                   gro_key &k) {
-    rxg_segment s;
-    const uint32_t i = vals[j];
-    const uint8_t *f = pkts + ((uint64_t)off[i] << unit_log2);
-    const uint32_t cap = len[i];
-    auto b = [&](uint32_t q) -> uint32_t { return q < cap ? (uint32_t)f[q] : 0u; };
-    const uint32_t tl = (b(16) << 8) | b(17);
-    s.frame = i;
-    s.flow = keys[j];
-    s.seq = (b(38) << 24) | (b(39) << 16) | (b(40) << 8) | b(41);
-    s.ack = (b(42) << 24) | (b(43) << 16) | (b(44) << 8) | b(45);
-    s.hl = (uint8_t)(b(46) >> 4);
-    s.flags = (uint8_t)b(47);
-    s.plen = (int32_t)tl - 20 - 4 * (int32_t)s.hl;
-    s.sport = (uint16_t)(b(34) | (b(35) << 8));
-    s.dport = (uint16_t)(b(36) | (b(37) << 8));
-    const uint32_t from = 34u + 4u * s.hl;
-    const uint32_t avail = cap > from ? cap - from : 0u;
-    const uint32_t keep = ((s.flags & 0x08u) && s.plen > 0) ? min((uint32_t)s.plen, avail) : 0u;
+    const ss_frame d = ss_decode(pkts, off, len, unit_log2, keys, vals, j);
+    const uint32_t keep = ss_keep(d);
+    rxg_segment s = d.s;
     s.ncopy = (uint16_t)keep;
-    s.offset = 0u;
     k.flow = s.flow;
-    k.sip = b(26) | (b(27) << 8) | (b(28) << 16) | (b(29) << 24);
+    k.sip = d.sip;
     k.ports = (uint32_t)s.sport | ((uint32_t)s.dport << 16);
     k.ack = s.ack;
     k.seq = s.seq;
@@ -492,8 +519,8 @@ __global__ __launch_bounds__(SS_THREADS) void gro_record_kernel(
     const bool link = j && p.merge && k.merge && p.flow == k.flow && p.sip == k.sip &&
                       p.ports == k.ports && p.ack == k.ack && k.seq == p.next_seq;
     uint32_t gsum, hmax;
-    const uint32_t ginc = gro_block_scan<false>(c, ws_g, gsum);
-    const uint32_t hinc = gro_block_scan<true>((j < nseg && !link) ? j + 1u : 0u, ws_h, hmax);
+    const uint32_t ginc = ss_block_scan<false>(c, ws_g, gsum);
+    const uint32_t hinc = ss_block_scan<true>((j < nseg && !link) ? j + 1u : 0u, ws_h, hmax);
     if (j < nseg) {
         gl[j] = ginc - c;
         hd[j] = hinc;
@@ -532,7 +559,7 @@ __global__ __launch_bounds__(SS_THREADS) void gro_runhead_kernel(
         }
     }
     uint32_t total;
-    const uint32_t inc = gro_block_scan<false>(rh, ws, total);
+    const uint32_t inc = ss_block_scan<false>(rh, ws, total);
     if (j < nseg) rl[j] = inc | (rh ? GRO_HEADBIT : 0u);
     if (t == 0u) bR[blockIdx.x] = total;
 }
@@ -580,19 +607,16 @@ __global__ __launch_bounds__(SS_THREADS) void gro_run_kernel(
         padded = (x.bytes + 15u) & ~15u;
     }
     uint32_t total;
-    const uint32_t inc = gro_block_scan<false>(padded, ws, total);
+    const uint32_t inc = ss_block_scan<false>(padded, ws, total);
     if (r < nrun) ol[r] = inc - padded;
     if (t == 0u) bO[blockIdx.x] = total;
 }
 
 // a wave per segment (bO scanned, tot[2] = the payload bytes used): its
 // offset = its run's offset + the run's ncopy before it, at any byte phase;
-// then its payload, bytes [34 + 4*hl, + ncopy) of the frame: the bytes up to
-// the first 16-B boundary of the destination and those after the last one as
-// byte stores, the chunks between as 16-B stores (dword loads realigned with
-// v_alignbyte, the source at any phase now); the run's last segment zeroes the
-// bytes to the 16-B padded end.  Every byte has one writer and no lane reads
-// the destination.
+// then its payload, bytes [34 + 4*hl, + ncopy) of the frame (ss_copy_bytes);
+// the run's last segment zeroes the bytes to the 16-B padded end.  Every byte
+// has one writer and no lane reads the destination.
 __global__ __launch_bounds__(SS_THREADS) void gro_copy_kernel(
     const uint8_t *__restrict__ pkts, const uint32_t *__restrict__ off,
     const uint16_t *__restrict__ len, uint32_t unit_log2, const uint64_t *__restrict__ tot,
@@ -626,111 +650,11 @@ __global__ __launch_bounds__(SS_THREADS) void gro_copy_kernel(
         if (lane - 32u < ((16u - (uint32_t)(end & 15u)) & 15u)) payload[end + (lane - 32u)] = 0u;
     }
     if (!ncopy) return;
-    const uint8_t *f = pkts + ((uint64_t)off[s.frame] << unit_log2);
-    const uint32_t fcap = len[s.frame];
-    const uint32_t src = 34u + 4u * s.hl;
-    const uint32_t hlen = min(ncopy, (16u - (uint32_t)(o & 15u)) & 15u);
-    const uint32_t nb = (ncopy - hlen) >> 4, tb = hlen + 16u * nb, tlen = ncopy - tb;
-    if (lane < hlen) payload[o + lane] = src + lane < fcap ? f[src + lane] : (uint8_t)0u;
-    if (lane >= 16u && lane - 16u < tlen) {
-        const uint32_t q = tb + (lane - 16u);
-        payload[o + q] = src + q < fcap ? f[src + q] : (uint8_t)0u;
-    }
-    for (uint32_t c = lane; c < nb; c += 64u) {
-        const uint32_t a = src + hlen + 16u * c, a0 = a & ~3u, sh = a & 3u;
-        uint32_t wv[5];
-#pragma unroll
-        for (uint32_t q = 0; q < 5u; ++q) {
-            const uint32_t p = a0 + 4u * q;
-            wv[q] = p < fcap ? *reinterpret_cast<const uint32_t *>(f + p) : 0u;
-        }
-        uint32_t o4[4];
-#pragma unroll
-        for (uint32_t q = 0; q < 4u; ++q)
-            o4[q] = sh ? __builtin_amdgcn_alignbyte(wv[q + 1], wv[q], sh) : wv[q];
-        *reinterpret_cast<uint4 *>(payload + o + hlen + 16u * c) =
-            make_uint4(o4[0], o4[1], o4[2], o4[3]);
-    }
+    ss_copy_bytes(pkts + ((uint64_t)off[s.frame] << unit_log2), len[s.frame], 34u + 4u * s.hl, ncopy,
+                  payload, o, lane);
 }
 
 } // namespace
-
-// workspace: K4's, then five words per frame (gl, hd, rl, rfirst, ol), four
-// 64-bit block arrays (bG, bH, bR, bO) and the three 64-bit totals
-size_t rx_gro_ws_bytes(uint32_t n) {
-    const size_t nn = n ? n : 1;
-    return rx_segsort_ws_bytes(n) + 5 * ss_align(nn * 4) +
-           4 * ss_align((size_t)(ss_blocks(n) ? ss_blocks(n) : 1) * 8) + 256;
-}
-
-// d_totals: 4 (segments, payload bytes, overflow flag, runs)
-hipError_t rx_gro_launch(const uint8_t *pkts, const uint32_t *off, const uint16_t *len, uint32_t n,
-                         uint32_t unit_log2, const uint4 *verd, uint32_t nt, uint32_t W,
-                         rxg_segment *seg, rxg_tcp_run *run, uint8_t *payload, uint64_t cap,
-                         uint32_t *totals, void *ws, hipStream_t s) {
-    hipError_t e = hipMemsetAsync(totals, 0, 4 * sizeof(uint32_t), s);
-    if (e != hipSuccess || n == 0 || nt == 0) return e;
-    const size_t nn = ss_align((size_t)n * 4);
-    uint8_t *w8 = static_cast<uint8_t *>(ws);
-    uint32_t *ka = reinterpret_cast<uint32_t *>(w8), *va = reinterpret_cast<uint32_t *>(w8 + nn);
-    uint32_t *kb = reinterpret_cast<uint32_t *>(w8 + 2 * nn), *vb = reinterpret_cast<uint32_t *>(w8 + 3 * nn);
-    const uint32_t ntiles = ss_tiles(n), nblk = ss_blocks(n);
-    uint32_t *hist = reinterpret_cast<uint32_t *>(w8 + 4 * nn);
-    uint8_t *g8 = w8 + rx_segsort_ws_bytes(n);
-    uint32_t *gl = reinterpret_cast<uint32_t *>(g8), *hd = reinterpret_cast<uint32_t *>(g8 + nn);
-    uint32_t *rl = reinterpret_cast<uint32_t *>(g8 + 2 * nn);
-    uint32_t *rfirst = reinterpret_cast<uint32_t *>(g8 + 3 * nn);
-    uint32_t *ol = reinterpret_cast<uint32_t *>(g8 + 4 * nn);
-    const size_t nb8 = ss_align((size_t)nblk * 8);
-    uint64_t *bG = reinterpret_cast<uint64_t *>(g8 + 5 * nn);
-    uint64_t *bH = reinterpret_cast<uint64_t *>(g8 + 5 * nn + nb8);
-    uint64_t *bR = reinterpret_cast<uint64_t *>(g8 + 5 * nn + 2 * nb8);
-    uint64_t *bO = reinterpret_cast<uint64_t *>(g8 + 5 * nn + 3 * nb8);
-    uint64_t *tot = reinterpret_cast<uint64_t *>(g8 + 5 * nn + 4 * nb8); // {sum of ncopy, runs, bytes used}
-    if ((e = hipMemsetAsync(tot, 0, 3 * sizeof(uint64_t), s)) != hipSuccess) return e;
-    // the sort, as in rx_segsort_launch
-    const uint32_t bits = 32u - (uint32_t)__builtin_clz(nt);
-    const uint32_t passes = (bits + 7u) / 8u;
-    const uint32_t *kin = nullptr, *vin = nullptr;
-    uint32_t *kout = ka, *vout = va;
-    for (uint32_t p = 0; p < passes; ++p) {
-        const uint32_t shift = 8u * p;
-        if (p == 0)
-            hipLaunchKernelGGL(ss_hist_kernel<true>, dim3(ntiles), dim3(SS_THREADS), 0, s, verd,
-                               nullptr, n, nt, shift, ntiles, hist, totals);
-        else
-            hipLaunchKernelGGL(ss_hist_kernel<false>, dim3(ntiles), dim3(SS_THREADS), 0, s, verd,
-                               kin, n, nt, shift, ntiles, hist, totals);
-        hipLaunchKernelGGL(ss_scan_kernel, dim3(1), dim3(1024), 0, s, hist, SS_DIGITS * ntiles,
-                           nullptr);
-        if (p == 0)
-            hipLaunchKernelGGL(ss_scatter_kernel<true>, dim3(ntiles), dim3(SS_THREADS), 0, s, verd,
-                               nullptr, nullptr, n, nt, shift, ntiles, hist, kout, vout);
-        else
-            hipLaunchKernelGGL(ss_scatter_kernel<false>, dim3(ntiles), dim3(SS_THREADS), 0, s, verd,
-                               kin, vin, n, nt, shift, ntiles, hist, kout, vout);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        kin = kout, vin = vout;
-        kout = (kout == ka) ? kb : ka;
-        vout = (vout == va) ? vb : va;
-    }
-    hipLaunchKernelGGL(gro_record_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, pkts, off, len,
-                       unit_log2, kin, vin, totals, seg, gl, hd, bG, bH);
-    hipLaunchKernelGGL(gro_scan_kernel, dim3(2), dim3(1024), 0, s, bG, bH, totals, tot);
-    hipLaunchKernelGGL(gro_runhead_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, seg, totals, W, gl,
-                       hd, bG, bH, rl, bR);
-    hipLaunchKernelGGL(gro_scan_kernel, dim3(1), dim3(1024), 0, s, bR, nullptr, totals, tot + 1);
-    hipLaunchKernelGGL(gro_runid_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, totals, tot, rl, bR,
-                       rfirst);
-    hipLaunchKernelGGL(gro_run_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, totals, tot, gl, bG,
-                       rfirst, run, ol, bO);
-    hipLaunchKernelGGL(gro_scan_kernel, dim3(1), dim3(1024), 0, s, bO, nullptr,
-                       reinterpret_cast<const uint32_t *>(tot + 1), tot + 2);
-    hipLaunchKernelGGL(gro_copy_kernel, dim3((uint32_t)(((uint64_t)n + 3) / 4)), dim3(SS_THREADS), 0,
-                       s, pkts, off, len, unit_log2, tot, gl, bG, rl, rfirst, ol, bO, seg, run,
-                       payload, cap, totals);
-    return hipGetLastError();
-}
 
 // ---- Sequence ordering (opt-in): a permutation stage between the sort and
 // the record stage (the rule: include/rxgpu.h, "TCP sequence ordering";
@@ -749,67 +673,22 @@ hipError_t rx_gro_launch(const uint8_t *pkts, const uint32_t *off, const uint16_
 // arrays.  No group is walked: one connection may own the whole burst.
 namespace {
 
-// what decides a record's group, and its seq
-struct ord_key {
-    uint32_t flow, sip, ports, movable, seq;
-};
-
-// sorted segment j's group key, bytes past the capture read as 0
-// (ss_record_kernel's rule)
-__device__ __forceinline__ ord_key ord_decode(const uint8_t *__restrict__ pkts,
-                                              const uint32_t *__restrict__ off,
-                                              const uint16_t *__restrict__ len, uint32_t unit_log2,
-                                              const uint32_t *__restrict__ keys,
-                                              const uint32_t *__restrict__ vals, uint32_t j) {
-    const uint32_t i = vals[j];
-    const uint8_t *f = pkts + ((uint64_t)off[i] << unit_log2);
-    const uint32_t cap = len[i];
-    auto b = [&](uint32_t q) -> uint32_t { return q < cap ? (uint32_t)f[q] : 0u; };
-    ord_key k;
-    k.flow = keys[j];
-    k.sip = b(26) | (b(27) << 8) | (b(28) << 16) | (b(29) << 24);
-    k.ports = b(34) | (b(35) << 8) | (b(36) << 16) | (b(37) << 24);
-    k.movable = (b(47) & 0x06u) == 0u; // neither SYN nor RST
-    k.seq = (b(38) << 24) | (b(39) << 16) | (b(40) << 8) | b(41);
-    return k;
-}
-
-// round 1: sq[j] = seq; hl[j] = 1 + the last group head at or before j inside
-// the block (0: none yet); bH[block] = the block's last head; bZ[block] = 0
-// (the sum half of gro_scan_kernel runs beside the max half, on zeros)
+// round 1: sq[j] = seq; hl[j], bH[block] and bZ[block] from ss_group_head
 __global__ __launch_bounds__(SS_THREADS) void ord_head_kernel(
     const uint8_t *__restrict__ pkts, const uint32_t *__restrict__ off,
     const uint16_t *__restrict__ len, uint32_t unit_log2, const uint32_t *__restrict__ keys,
     const uint32_t *__restrict__ vals, const uint32_t *__restrict__ totals,
     uint32_t *__restrict__ sq, uint32_t *__restrict__ hl, uint64_t *__restrict__ bH,
     uint64_t *__restrict__ bZ) {
-    __shared__ uint32_t pf[SS_THREADS + 1u], ps[SS_THREADS + 1u], pp[SS_THREADS + 1u],
-        pm[SS_THREADS + 1u];
-    __shared__ uint32_t ws[SS_THREADS / 64u];
     const uint32_t nseg = totals[0];
-    const uint32_t t = threadIdx.x;
-    const uint32_t j0 = blockIdx.x * SS_THREADS, j = j0 + t;
+    const uint32_t j0 = blockIdx.x * SS_THREADS, j = j0 + threadIdx.x;
     if (j0 >= nseg) return; // (uniform)
-    ord_key k = {0u, 0u, 0u, 0u, 0u};
-    if (j < nseg) k = ord_decode(pkts, off, len, unit_log2, keys, vals, j);
-    pf[t + 1u] = k.flow, ps[t + 1u] = k.sip, pp[t + 1u] = k.ports, pm[t + 1u] = k.movable;
-    if (t == 0u) { // the block's predecessor record, decoded again
-        ord_key p = {0u, 0u, 0u, 0u, 0u};
-        if (j0) p = ord_decode(pkts, off, len, unit_log2, keys, vals, j0 - 1u);
-        pf[0] = p.flow, ps[0] = p.sip, pp[0] = p.ports, pm[0] = p.movable;
-    }
-    __syncthreads();
-    const bool head = !j || !k.movable || !pm[t] || pf[t] != k.flow || ps[t] != k.sip ||
-                      pp[t] != k.ports;
-    uint32_t hmax;
-    const uint32_t hinc = gro_block_scan<true>((j < nseg && head) ? j + 1u : 0u, ws, hmax);
+    ss_frame d = {};
+    if (j < nseg) d = ss_decode(pkts, off, len, unit_log2, keys, vals, j);
+    const uint32_t hinc = ss_group_head(pkts, off, len, unit_log2, keys, vals, nseg, d, bH, bZ);
     if (j < nseg) {
-        sq[j] = k.seq;
+        sq[j] = d.s.seq;
         hl[j] = hinc;
-    }
-    if (t == 0u) {
-        bH[blockIdx.x] = hmax;
-        bZ[blockIdx.x] = 0u;
     }
 }
 
@@ -877,142 +756,6 @@ __global__ __launch_bounds__(SS_THREADS) void ord_apply_kernel(
 
 } // namespace
 
-// workspace: the coalescing form's, then seven words per frame (seq, local
-// head, head index, and the (key, position) pair twice), two 64-bit block
-// arrays and the flag
-size_t rx_order_ws_bytes(uint32_t n) {
-    const size_t nn = n ? n : 1;
-    return rx_gro_ws_bytes(n) + 7 * ss_align(nn * 4) +
-           2 * ss_align((size_t)(ss_blocks(n) ? ss_blocks(n) : 1) * 8) + 256;
-}
-
-// K4 (W == 0; payload NULL: records only) or its coalescing form (W != 0) on
-// the sequence-ordered segments; d_totals: 5 (segments, payload bytes,
-// overflow flag, runs, moved)
-hipError_t rx_order_launch(const uint8_t *pkts, const uint32_t *off, const uint16_t *len, uint32_t n,
-                           uint32_t unit_log2, const uint4 *verd, uint32_t nt, uint32_t W,
-                           rxg_segment *seg, rxg_tcp_run *run, uint8_t *payload, uint64_t cap,
-                           uint32_t *totals, void *ws, hipStream_t s) {
-    hipError_t e = hipMemsetAsync(totals, 0, 5 * sizeof(uint32_t), s);
-    if (e != hipSuccess || n == 0 || nt == 0) return e;
-    const size_t nn = ss_align((size_t)n * 4);
-    uint8_t *w8 = static_cast<uint8_t *>(ws);
-    uint32_t *ka = reinterpret_cast<uint32_t *>(w8), *va = reinterpret_cast<uint32_t *>(w8 + nn);
-    uint32_t *kb = reinterpret_cast<uint32_t *>(w8 + 2 * nn), *vb = reinterpret_cast<uint32_t *>(w8 + 3 * nn);
-    const uint32_t ntiles = ss_tiles(n), nblk = ss_blocks(n);
-    uint32_t *hist = reinterpret_cast<uint32_t *>(w8 + 4 * nn);
-    uint32_t *tsum = reinterpret_cast<uint32_t *>(w8 + 4 * nn + ss_align((size_t)SS_DIGITS * ntiles * 4));
-    const size_t nb8 = ss_align((size_t)nblk * 8);
-    uint8_t *o8 = w8 + rx_gro_ws_bytes(n);
-    uint32_t *sq = reinterpret_cast<uint32_t *>(o8), *hl = reinterpret_cast<uint32_t *>(o8 + nn);
-    uint32_t *hk = reinterpret_cast<uint32_t *>(o8 + 2 * nn);
-    uint32_t *oka = reinterpret_cast<uint32_t *>(o8 + 3 * nn), *pa = reinterpret_cast<uint32_t *>(o8 + 4 * nn);
-    uint32_t *okb = reinterpret_cast<uint32_t *>(o8 + 5 * nn), *pb = reinterpret_cast<uint32_t *>(o8 + 6 * nn);
-    uint64_t *bH = reinterpret_cast<uint64_t *>(o8 + 7 * nn);
-    uint64_t *bZ = reinterpret_cast<uint64_t *>(o8 + 7 * nn + nb8);
-    uint32_t *flag = reinterpret_cast<uint32_t *>(o8 + 7 * nn + 2 * nb8);
-    if ((e = hipMemsetAsync(flag, 0, sizeof(uint32_t), s)) != hipSuccess) return e;
-    // one stable radix pass of K4's sort over digit `shift` of (ki, vi)
-    auto pass = [&](const uint32_t *ki, const uint32_t *vi, uint32_t shift, uint32_t *ko,
-                    uint32_t *vo) -> hipError_t {
-        hipLaunchKernelGGL(ss_hist_kernel<false>, dim3(ntiles), dim3(SS_THREADS), 0, s, verd, ki, n,
-                           nt, shift, ntiles, hist, totals);
-        hipLaunchKernelGGL(ss_scan_kernel, dim3(1), dim3(1024), 0, s, hist, SS_DIGITS * ntiles,
-                           nullptr);
-        hipLaunchKernelGGL(ss_scatter_kernel<false>, dim3(ntiles), dim3(SS_THREADS), 0, s, verd, ki,
-                           vi, n, nt, shift, ntiles, hist, ko, vo);
-        return hipGetLastError();
-    };
-    // the sort, as in rx_segsort_launch
-    const uint32_t bits = 32u - (uint32_t)__builtin_clz(nt);
-    const uint32_t passes = (bits + 7u) / 8u;
-    const uint32_t *kin = nullptr, *vin = nullptr;
-    uint32_t *kout = ka, *vout = va;
-    for (uint32_t p = 0; p < passes; ++p) {
-        const uint32_t shift = 8u * p;
-        if (p == 0) {
-            hipLaunchKernelGGL(ss_hist_kernel<true>, dim3(ntiles), dim3(SS_THREADS), 0, s, verd,
-                               nullptr, n, nt, shift, ntiles, hist, totals);
-            hipLaunchKernelGGL(ss_scan_kernel, dim3(1), dim3(1024), 0, s, hist, SS_DIGITS * ntiles,
-                               nullptr);
-            hipLaunchKernelGGL(ss_scatter_kernel<true>, dim3(ntiles), dim3(SS_THREADS), 0, s, verd,
-                               nullptr, nullptr, n, nt, shift, ntiles, hist, kout, vout);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-        } else if ((e = pass(kin, vin, shift, kout, vout)) != hipSuccess) {
-            return e;
-        }
-        kin = kout, vin = vout;
-        kout = (kout == ka) ? kb : ka;
-        vout = (vout == va) ? vb : va;
-    }
-    // the permutation: keys, four key passes (a -> b -> a -> b -> a), the head
-    // index as the key, its passes (positions 0 .. n-1)
-    hipLaunchKernelGGL(ord_head_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, pkts, off, len, unit_log2,
-                       kin, vin, totals, sq, hl, bH, bZ);
-    hipLaunchKernelGGL(gro_scan_kernel, dim3(2), dim3(1024), 0, s, bZ, bH, totals, nullptr);
-    hipLaunchKernelGGL(ord_key_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, totals, n, sq, hl, bH, oka,
-                       hk, pa, flag);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    uint32_t *ok = oka, *pv = pa, *ok2 = okb, *pv2 = pb;
-    for (uint32_t p = 0; p < 4u; ++p) {
-        if ((e = pass(ok, pv, 8u * p, ok2, pv2)) != hipSuccess) return e;
-        uint32_t *x = ok; ok = ok2, ok2 = x;
-        x = pv, pv = pv2, pv2 = x;
-    }
-    hipLaunchKernelGGL(ord_headkey_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, n, flag, hk, pv, ok);
-    const uint32_t hbits = n > 1u ? 32u - (uint32_t)__builtin_clz(n - 1u) : 1u;
-    for (uint32_t p = 0; p < (hbits + 7u) / 8u; ++p) {
-        if ((e = pass(ok, pv, 8u * p, ok2, pv2)) != hipSuccess) return e;
-        uint32_t *x = ok; ok = ok2, ok2 = x;
-        x = pv, pv = pv2, pv2 = x;
-    }
-    hipLaunchKernelGGL(ord_apply_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, n, flag, pv, kin, vin,
-                       kout, vout, totals);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    kin = kout, vin = vout;
-    if (!W) { // K4's record stage, as in rx_segsort_launch
-        if (!payload) {
-            hipLaunchKernelGGL(ss_record_kernel<true>, dim3(nblk), dim3(SS_THREADS), 0, s, pkts, off,
-                               len, unit_log2, kin, vin, totals, seg, tsum);
-            return hipGetLastError();
-        }
-        hipLaunchKernelGGL(ss_record_kernel<false>, dim3(nblk), dim3(SS_THREADS), 0, s, pkts, off,
-                           len, unit_log2, kin, vin, totals, seg, tsum);
-        hipLaunchKernelGGL(ss_scan_kernel, dim3(1), dim3(1024), 0, s, tsum, nblk, totals + 1);
-        hipLaunchKernelGGL(ss_copy_kernel, dim3((uint32_t)(((uint64_t)n + 3) / 4)), dim3(SS_THREADS),
-                           0, s, pkts, off, len, unit_log2, tsum, seg, payload, cap, totals);
-        return hipGetLastError();
-    }
-    // the coalescing stage, as in rx_gro_launch
-    uint8_t *g8 = w8 + rx_segsort_ws_bytes(n);
-    uint32_t *gl = reinterpret_cast<uint32_t *>(g8), *hd = reinterpret_cast<uint32_t *>(g8 + nn);
-    uint32_t *rl = reinterpret_cast<uint32_t *>(g8 + 2 * nn);
-    uint32_t *rfirst = reinterpret_cast<uint32_t *>(g8 + 3 * nn);
-    uint32_t *ol = reinterpret_cast<uint32_t *>(g8 + 4 * nn);
-    uint64_t *bG = reinterpret_cast<uint64_t *>(g8 + 5 * nn);
-    uint64_t *bHg = reinterpret_cast<uint64_t *>(g8 + 5 * nn + nb8);
-    uint64_t *bR = reinterpret_cast<uint64_t *>(g8 + 5 * nn + 2 * nb8);
-    uint64_t *bO = reinterpret_cast<uint64_t *>(g8 + 5 * nn + 3 * nb8);
-    uint64_t *tot = reinterpret_cast<uint64_t *>(g8 + 5 * nn + 4 * nb8); // {sum of ncopy, runs, bytes used}
-    if ((e = hipMemsetAsync(tot, 0, 3 * sizeof(uint64_t), s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(gro_record_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, pkts, off, len,
-                       unit_log2, kin, vin, totals, seg, gl, hd, bG, bHg);
-    hipLaunchKernelGGL(gro_scan_kernel, dim3(2), dim3(1024), 0, s, bG, bHg, totals, tot);
-    hipLaunchKernelGGL(gro_runhead_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, seg, totals, W, gl,
-                       hd, bG, bHg, rl, bR);
-    hipLaunchKernelGGL(gro_scan_kernel, dim3(1), dim3(1024), 0, s, bR, nullptr, totals, tot + 1);
-    hipLaunchKernelGGL(gro_runid_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, totals, tot, rl, bR,
-                       rfirst);
-    hipLaunchKernelGGL(gro_run_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, totals, tot, gl, bG,
-                       rfirst, run, ol, bO);
-    hipLaunchKernelGGL(gro_scan_kernel, dim3(1), dim3(1024), 0, s, bO, nullptr,
-                       reinterpret_cast<const uint32_t *>(tot + 1), tot + 2);
-    hipLaunchKernelGGL(gro_copy_kernel, dim3((uint32_t)(((uint64_t)n + 3) / 4)), dim3(SS_THREADS), 0,
-                       s, pkts, off, len, unit_log2, tot, gl, bG, rl, rfirst, ol, bO, seg, run,
-                       payload, cap, totals);
-    return hipGetLastError();
-}
-
 // ---- Stream assembly (opt-in): after the sort and the ordering stage, each
 // connection's segments of the burst laid down as contiguous byte ranges with
 // duplicates dropped, overlaps trimmed and a new range at every hole (the
@@ -1055,68 +798,31 @@ __device__ __forceinline__ void asm_wave_scan(bool &f, uint64_t &v) {
 }
 
 // round 1: the ordered form's record of position j (ncopy and offset in
-// asm_copy_kernel), dl[j] = dlen and the ASM_USABLE / ASM_FIN bits, hl[j] =
-// 1 + the last group head at or before j inside the block (0: none yet);
-// bH[block] = the block's last head, bZ[block] = 0 (ord_head_kernel's pair)
+// asm_copy_kernel), dl[j] = dlen and the ASM_USABLE / ASM_FIN bits; hl[j],
+// bH[block] and bZ[block] from ss_group_head
 __global__ __launch_bounds__(SS_THREADS) void asm_record_kernel(
     const uint8_t *__restrict__ pkts, const uint32_t *__restrict__ off,
     const uint16_t *__restrict__ len, uint32_t unit_log2, const uint32_t *__restrict__ keys,
     const uint32_t *__restrict__ vals, const uint32_t *__restrict__ totals,
     rxg_segment *__restrict__ seg, uint32_t *__restrict__ dl, uint32_t *__restrict__ hl,
     uint64_t *__restrict__ bH, uint64_t *__restrict__ bZ) {
-    __shared__ uint32_t pf[SS_THREADS + 1u], ps[SS_THREADS + 1u], pp[SS_THREADS + 1u],
-        pm[SS_THREADS + 1u];
-    __shared__ uint32_t ws[SS_THREADS / 64u];
     const uint32_t nseg = totals[0];
-    const uint32_t t = threadIdx.x;
-    const uint32_t j0 = blockIdx.x * SS_THREADS, j = j0 + t;
+    const uint32_t j0 = blockIdx.x * SS_THREADS, j = j0 + threadIdx.x;
     if (j0 >= nseg) return; // (uniform)
-    ord_key k = {0u, 0u, 0u, 0u, 0u};
+    ss_frame k = {};
     if (j < nseg) {
-        k = ord_decode(pkts, off, len, unit_log2, keys, vals, j);
-        const uint32_t i = vals[j];
-        const uint8_t *f = pkts + ((uint64_t)off[i] << unit_log2);
-        const uint32_t cap = len[i];
-        auto b = [&](uint32_t q) -> uint32_t { return q < cap ? (uint32_t)f[q] : 0u; };
-        const uint32_t tl = (b(16) << 8) | b(17);
-        rxg_segment s;
-        s.frame = i;
-        s.flow = k.flow;
-        s.seq = k.seq;
-        s.ack = (b(42) << 24) | (b(43) << 16) | (b(44) << 8) | b(45);
-        s.hl = (uint8_t)(b(46) >> 4);
-        s.flags = (uint8_t)b(47);
-        s.plen = (int32_t)tl - 20 - 4 * (int32_t)s.hl;
-        s.offset = 0u;
-        s.sport = (uint16_t)(k.ports & 0xFFFFu);
-        s.dport = (uint16_t)(k.ports >> 16);
-        s.ncopy = 0u;
+        k = ss_decode(pkts, off, len, unit_log2, keys, vals, j);
+        const rxg_segment &s = k.s;
         seg[j] = s;
-        const uint32_t from = 34u + 4u * s.hl;
-        const uint32_t avail = cap > from ? cap - from : 0u;
-        const bool usable = s.plen <= 0 || avail >= (uint32_t)s.plen;
+        const bool usable = s.plen <= 0 || k.avail >= (uint32_t)s.plen;
         // (a SYN or RST record is left alone: no data, no FIN)
         uint32_t d = (k.movable && usable && s.plen > 0) ? (uint32_t)s.plen : 0u;
         if (usable) d |= ASM_USABLE;
         if (k.movable && usable && (s.flags & 0x01u)) d |= ASM_FIN;
         dl[j] = d;
     }
-    pf[t + 1u] = k.flow, ps[t + 1u] = k.sip, pp[t + 1u] = k.ports, pm[t + 1u] = k.movable;
-    if (t == 0u) { // the block's predecessor record, decoded again
-        ord_key p = {0u, 0u, 0u, 0u, 0u};
-        if (j0) p = ord_decode(pkts, off, len, unit_log2, keys, vals, j0 - 1u);
-        pf[0] = p.flow, ps[0] = p.sip, pp[0] = p.ports, pm[0] = p.movable;
-    }
-    __syncthreads();
-    const bool head = !j || !k.movable || !pm[t] || pf[t] != k.flow || ps[t] != k.sip ||
-                      pp[t] != k.ports;
-    uint32_t hmax;
-    const uint32_t hinc = gro_block_scan<true>((j < nseg && head) ? j + 1u : 0u, ws, hmax);
+    const uint32_t hinc = ss_group_head(pkts, off, len, unit_log2, keys, vals, nseg, k, bH, bZ);
     if (j < nseg) hl[j] = hinc;
-    if (t == 0u) {
-        bH[blockIdx.x] = hmax;
-        bZ[blockIdx.x] = 0u;
-    }
 }
 
 // round 2 (bH scanned): av[j] = a[j]; il[j] = the maximum of end over the
@@ -1281,8 +987,8 @@ __global__ __launch_bounds__(SS_THREADS) void asm_head_kernel(
         fl[j] = (st ? ASM_F_START : 0u) | (r.hole ? ASM_F_HOLE : 0u) | (r.finok ? ASM_F_FINOK : 0u);
     }
     uint32_t rsum, tsum;
-    const uint32_t rinc = gro_block_scan<false>(start, ws_r, rsum);
-    const uint32_t tinc = gro_block_scan<false>(take, ws_t, tsum);
+    const uint32_t rinc = ss_block_scan<false>(start, ws_r, rsum);
+    const uint32_t tinc = ss_block_scan<false>(take, ws_t, tsum);
     if (j < nseg) {
         sl[j] = rinc;
         tl[j] = tinc - take;
@@ -1344,19 +1050,16 @@ __global__ __launch_bounds__(SS_THREADS) void asm_stream_kernel(
         padded = (x.bytes + 15u) & ~15u;
     }
     uint32_t total;
-    const uint32_t inc = gro_block_scan<false>(padded, ws, total);
+    const uint32_t inc = ss_block_scan<false>(padded, ws, total);
     if (r < nst) ol[r] = inc - padded;
     if (t == 0u) bO[blockIdx.x] = total;
 }
 
 // a wave per record (bO scanned, tot[2] = the payload bytes used): its offset
 // = its stream's offset + the stream's take before it, at any byte phase; then
-// its take bytes, [34 + 4*hl + skip, + take) of the frame, as gro_copy_kernel
-// copies a payload: the bytes up to the first 16-B boundary of the destination
-// and those after the last one as byte stores, the chunks between as 16-B
-// stores (dword loads realigned with v_alignbyte); the stream's last record
-// zeroes the bytes to the 16-B padded end.  Every byte has one writer and no
-// lane reads the destination.
+// its take bytes, [34 + 4*hl + skip, + take) of the frame (ss_copy_bytes); the
+// stream's last record zeroes the bytes to the 16-B padded end.  Every byte
+// has one writer and no lane reads the destination.
 __global__ __launch_bounds__(SS_THREADS) void asm_copy_kernel(
     const uint8_t *__restrict__ pkts, const uint32_t *__restrict__ off,
     const uint16_t *__restrict__ len, uint32_t unit_log2, const uint64_t *__restrict__ tot,
@@ -1392,45 +1095,301 @@ __global__ __launch_bounds__(SS_THREADS) void asm_copy_kernel(
         if (lane - 32u < ((16u - (uint32_t)(end & 15u)) & 15u)) payload[end + (lane - 32u)] = 0u;
     }
     if (!take) return;
-    const uint8_t *f = pkts + ((uint64_t)off[frame] << unit_log2);
-    const uint32_t fcap = len[frame];
-    const uint32_t src = 34u + 4u * hl + ((dl[j] & 0xFFFFu) - take);
-    const uint32_t hlen = min(take, (16u - (uint32_t)(o & 15u)) & 15u);
-    const uint32_t nb = (take - hlen) >> 4, tb = hlen + 16u * nb, tlen = take - tb;
-    if (lane < hlen) payload[o + lane] = src + lane < fcap ? f[src + lane] : (uint8_t)0u;
-    if (lane >= 16u && lane - 16u < tlen) {
-        const uint32_t q = tb + (lane - 16u);
-        payload[o + q] = src + q < fcap ? f[src + q] : (uint8_t)0u;
-    }
-    for (uint32_t c = lane; c < nb; c += 64u) {
-        const uint32_t a = src + hlen + 16u * c, a0 = a & ~3u, sh = a & 3u;
-        uint32_t wv[5];
-#pragma unroll
-        for (uint32_t q = 0; q < 5u; ++q) {
-            const uint32_t p = a0 + 4u * q;
-            wv[q] = p < fcap ? *reinterpret_cast<const uint32_t *>(f + p) : 0u;
-        }
-        uint32_t o4[4];
-#pragma unroll
-        for (uint32_t q = 0; q < 4u; ++q)
-            o4[q] = sh ? __builtin_amdgcn_alignbyte(wv[q + 1], wv[q], sh) : wv[q];
-        *reinterpret_cast<uint4 *>(payload + o + hlen + 16u * c) =
-            make_uint4(o4[0], o4[1], o4[2], o4[3]);
-    }
+    ss_copy_bytes(pkts + ((uint64_t)off[frame] << unit_log2), len[frame],
+                  34u + 4u * hl + ((dl[j] & 0xFFFFu) - take), take, payload, o, lane);
 }
 
 } // namespace
 
-// workspace: the ordering form's, then ten words and one 64-bit word per frame
-// (dl, hl, av, tk, s32, fl, sl, sfirst, ol, tl; il), seven 64-bit block
-// arrays (bH, bZ, bV, bF, bR, bT, bO) and the three 64-bit totals
-size_t rx_assemble_ws_bytes(uint32_t n) {
-    const size_t nn = n ? n : 1;
-    return rx_order_ws_bytes(n) + 10 * ss_align(nn * 4) + ss_align(nn * 8) +
-           7 * ss_align((size_t)(ss_blocks(n) ? ss_blocks(n) : 1) * 8) + 256;
+// ---- The host side: one workspace description, the stages, and the four
+// entry points as compositions of them.
+namespace {
+
+inline uint32_t ss_tiles(uint32_t n) { return (uint32_t)(((uint64_t)n + SS_TILE - 1) / SS_TILE); }
+inline uint32_t ss_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + SS_THREADS - 1) / SS_THREADS); }
+inline size_t ss_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// every region of the workspace of a burst of n frames, in layout order; a
+// form's workspace is the prefix up to its own region's end, so the assembly
+// form reserves the coalescing region without using it
+struct k4_ws {
+    // the sort: keys and values twice (ping-pong), the digit histograms, the
+    // record blocks' payload sizes
+    uint32_t *ka, *va, *kb, *vb, *hist, *tsum;
+    struct { // coalescing; tot = {sum of ncopy, runs, bytes used}
+        uint32_t *gl, *hd, *rl, *rfirst, *ol;
+        uint64_t *bG, *bH, *bR, *bO, *tot;
+    } g;
+    struct { // ordering: seq, local head, head index, the (key, position) pair twice
+        uint32_t *sq, *hl, *hk, *oka, *pa, *okb, *pb;
+        uint64_t *bH, *bZ;
+        uint32_t *flag;
+    } o;
+    struct { // assembly; tot = {sum of take, streams, bytes used}
+        uint32_t *dl, *hl, *av, *tk, *s32, *fl, *sl, *sfirst, *ol, *tl;
+        uint64_t *il, *bH, *bZ, *bV, *bF, *bR, *bT, *bO, *tot;
+    } a;
+    size_t end_sort, end_gro, end_order, end_assemble; // rx_*_ws_bytes(n)
+};
+
+// the one carve: every array starts 256-B aligned; ws may be null (the sizes only)
+k4_ws k4_carve(void *ws, uint32_t n) {
+    const size_t nn = n ? n : 1, ntiles = ss_tiles(n) ? ss_tiles(n) : 1,
+                 nblk = ss_blocks(n) ? ss_blocks(n) : 1;
+    const size_t frame4 = nn * 4, frame8 = nn * 8, blk8 = nblk * 8;
+    const uintptr_t base = reinterpret_cast<uintptr_t>(ws);
+    size_t at = 0;
+    auto take = [&](auto *&p, size_t bytes) {
+        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + at);
+        at += ss_align(bytes);
+    };
+    k4_ws w;
+    for (uint32_t **p : {&w.ka, &w.va, &w.kb, &w.vb}) take(*p, frame4);
+    take(w.hist, SS_DIGITS * ntiles * 4);
+    take(w.tsum, nblk * 4);
+    w.end_sort = at;
+    for (uint32_t **p : {&w.g.gl, &w.g.hd, &w.g.rl, &w.g.rfirst, &w.g.ol}) take(*p, frame4);
+    for (uint64_t **p : {&w.g.bG, &w.g.bH, &w.g.bR, &w.g.bO}) take(*p, blk8);
+    take(w.g.tot, 3 * 8);
+    w.end_gro = at;
+    for (uint32_t **p : {&w.o.sq, &w.o.hl, &w.o.hk, &w.o.oka, &w.o.pa, &w.o.okb, &w.o.pb})
+        take(*p, frame4);
+    for (uint64_t **p : {&w.o.bH, &w.o.bZ}) take(*p, blk8);
+    take(w.o.flag, 4);
+    w.end_order = at;
+    for (uint32_t **p : {&w.a.dl, &w.a.hl, &w.a.av, &w.a.tk, &w.a.s32, &w.a.fl, &w.a.sl,
+                         &w.a.sfirst, &w.a.ol, &w.a.tl})
+        take(*p, frame4);
+    take(w.a.il, frame8);
+    for (uint64_t **p : {&w.a.bH, &w.a.bZ, &w.a.bV, &w.a.bF, &w.a.bR, &w.a.bT, &w.a.bO})
+        take(*p, blk8);
+    take(w.a.tot, 3 * 8);
+    w.end_assemble = at;
+    return w;
 }
 
-// the sort, the ordering stage and the stream assembly; d_totals: 6 (segments,
+// what every stage of one call works on
+struct k4_call {
+    const uint8_t *pkts;
+    const uint32_t *off;
+    const uint16_t *len;
+    uint32_t n, unit_log2;
+    const uint4 *verd;
+    uint32_t nt;
+    uint32_t *totals;
+    hipStream_t s;
+    uint32_t ntiles, nblk;
+    k4_ws w;
+};
+
+// a (keys, values) array pair of the sort
+struct k4_pair {
+    uint32_t *k, *v;
+};
+
+// one stable radix pass over digit `shift` of (ki, vi) into (ko, vo); the
+// first pass of the flow sort reads its keys from the verdicts instead
+hipError_t radix_pass(const k4_call &c, const uint32_t *ki, const uint32_t *vi, uint32_t shift,
+                      uint32_t *ko, uint32_t *vo, bool first) {
+    const dim3 grid(c.ntiles), block(SS_THREADS);
+    if (first)
+        hipLaunchKernelGGL(ss_hist_kernel<true>, grid, block, 0, c.s, c.verd, nullptr, c.n, c.nt, shift,
+                           c.ntiles, c.w.hist, c.totals);
+    else
+        hipLaunchKernelGGL(ss_hist_kernel<false>, grid, block, 0, c.s, c.verd, ki, c.n, c.nt, shift,
+                           c.ntiles, c.w.hist, c.totals);
+    hipLaunchKernelGGL(ss_scan_kernel, dim3(1), dim3(1024), 0, c.s, c.w.hist, SS_DIGITS * c.ntiles,
+                       nullptr);
+    if (first)
+        hipLaunchKernelGGL(ss_scatter_kernel<true>, grid, block, 0, c.s, c.verd, nullptr, nullptr, c.n,
+                           c.nt, shift, c.ntiles, c.w.hist, ko, vo);
+    else
+        hipLaunchKernelGGL(ss_scatter_kernel<false>, grid, block, 0, c.s, c.verd, ki, vi, c.n, c.nt,
+                           shift, c.ntiles, c.w.hist, ko, vo);
+    return hipGetLastError();
+}
+
+// `passes` radix passes from digit 0 up, ping-pong between cur and spare;
+// afterwards cur holds the result
+hipError_t radix_passes(const k4_call &c, k4_pair &cur, k4_pair &spare, uint32_t passes, bool verdicts) {
+    for (uint32_t p = 0; p < passes; ++p) {
+        const hipError_t e = radix_pass(c, cur.k, cur.v, 8u * p, spare.k, spare.v, verdicts && p == 0);
+        if (e != hipSuccess) return e;
+        const k4_pair x = cur;
+        cur = spare, spare = x;
+    }
+    return hipSuccess;
+}
+
+// the sort stage: the delivered segments by flow id (ids 0..nt-1 and the
+// sentinel nt: as many 8-bit digits as that needs); cur = the sorted (flow,
+// frame) arrays, spare = the free pair
+hipError_t sort_stage(const k4_call &c, k4_pair &cur, k4_pair &spare) {
+    const uint32_t bits = 32u - (uint32_t)__builtin_clz(c.nt);
+    cur = {c.w.kb, c.w.vb}, spare = {c.w.ka, c.w.va}; // (the first pass reads no input pair)
+    return radix_passes(c, cur, spare, (bits + 7u) / 8u, true);
+}
+
+// the ordering stage: the group heads, the keys, four key passes (a -> b -> a
+// -> b -> a), the head index as the key, its passes (positions 0 .. n-1), and
+// the sorted arrays gathered through the permutation into the free pair, which
+// becomes cur
+hipError_t order_stage(const k4_call &c, k4_pair &cur, k4_pair &spare) {
+    const dim3 grid(c.nblk), block(SS_THREADS);
+    const auto &o = c.w.o;
+    hipError_t e;
+    hipLaunchKernelGGL(ord_head_kernel, grid, block, 0, c.s, c.pkts, c.off, c.len, c.unit_log2, cur.k,
+                       cur.v, c.totals, o.sq, o.hl, o.bH, o.bZ);
+    hipLaunchKernelGGL(gro_scan_kernel, dim3(2), dim3(1024), 0, c.s, o.bZ, o.bH, c.totals, nullptr);
+    hipLaunchKernelGGL(ord_key_kernel, grid, block, 0, c.s, c.totals, c.n, o.sq, o.hl, o.bH, o.oka,
+                       o.hk, o.pa, o.flag);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    k4_pair key = {o.oka, o.pa}, key2 = {o.okb, o.pb};
+    if ((e = radix_passes(c, key, key2, 4u, false)) != hipSuccess) return e;
+    hipLaunchKernelGGL(ord_headkey_kernel, grid, block, 0, c.s, c.n, o.flag, o.hk, key.v, key.k);
+    const uint32_t hbits = c.n > 1u ? 32u - (uint32_t)__builtin_clz(c.n - 1u) : 1u;
+    if ((e = radix_passes(c, key, key2, (hbits + 7u) / 8u, false)) != hipSuccess) return e;
+    hipLaunchKernelGGL(ord_apply_kernel, grid, block, 0, c.s, c.n, o.flag, key.v, cur.k, cur.v,
+                       spare.k, spare.v, c.totals);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    const k4_pair x = cur;
+    cur = spare, spare = x;
+    return hipSuccess;
+}
+
+// a wave per segment
+inline dim3 ss_copy_grid(uint32_t n) { return dim3((uint32_t)(((uint64_t)n + 3) / 4)); }
+
+// K4's record stage: the records in place (no payload buffer: offset = the
+// payload's offset in its frame), or the records, their offsets and the copy
+hipError_t record_stage(const k4_call &c, const k4_pair &cur, rxg_segment *seg, uint8_t *payload,
+                        uint64_t cap) {
+    const dim3 grid(c.nblk), block(SS_THREADS);
+    if (!payload) {
+        hipLaunchKernelGGL(ss_record_kernel<true>, grid, block, 0, c.s, c.pkts, c.off, c.len,
+                           c.unit_log2, cur.k, cur.v, c.totals, seg, c.w.tsum);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(ss_record_kernel<false>, grid, block, 0, c.s, c.pkts, c.off, c.len, c.unit_log2,
+                       cur.k, cur.v, c.totals, seg, c.w.tsum);
+    hipLaunchKernelGGL(ss_scan_kernel, dim3(1), dim3(1024), 0, c.s, c.w.tsum, c.nblk, c.totals + 1);
+    hipLaunchKernelGGL(ss_copy_kernel, ss_copy_grid(c.n), block, 0, c.s, c.pkts, c.off, c.len,
+                       c.unit_log2, c.w.tsum, seg, payload, cap, c.totals);
+    return hipGetLastError();
+}
+
+// the coalescing stage (g.tot cleared by the caller)
+hipError_t coalesce_stage(const k4_call &c, const k4_pair &cur, uint32_t W, rxg_segment *seg,
+                          rxg_tcp_run *run, uint8_t *payload, uint64_t cap) {
+    const dim3 grid(c.nblk), block(SS_THREADS), one(1), scan(1024);
+    const auto &g = c.w.g;
+    hipLaunchKernelGGL(gro_record_kernel, grid, block, 0, c.s, c.pkts, c.off, c.len, c.unit_log2,
+                       cur.k, cur.v, c.totals, seg, g.gl, g.hd, g.bG, g.bH);
+    hipLaunchKernelGGL(gro_scan_kernel, dim3(2), scan, 0, c.s, g.bG, g.bH, c.totals, g.tot);
+    hipLaunchKernelGGL(gro_runhead_kernel, grid, block, 0, c.s, seg, c.totals, W, g.gl, g.hd, g.bG,
+                       g.bH, g.rl, g.bR);
+    hipLaunchKernelGGL(gro_scan_kernel, one, scan, 0, c.s, g.bR, nullptr, c.totals, g.tot + 1);
+    hipLaunchKernelGGL(gro_runid_kernel, grid, block, 0, c.s, c.totals, g.tot, g.rl, g.bR, g.rfirst);
+    hipLaunchKernelGGL(gro_run_kernel, grid, block, 0, c.s, c.totals, g.tot, g.gl, g.bG, g.rfirst, run,
+                       g.ol, g.bO);
+    hipLaunchKernelGGL(gro_scan_kernel, one, scan, 0, c.s, g.bO, nullptr,
+                       reinterpret_cast<const uint32_t *>(g.tot + 1), g.tot + 2);
+    hipLaunchKernelGGL(gro_copy_kernel, ss_copy_grid(c.n), block, 0, c.s, c.pkts, c.off, c.len,
+                       c.unit_log2, g.tot, g.gl, g.bG, g.rl, g.rfirst, g.ol, g.bO, seg, run, payload,
+                       cap, c.totals);
+    return hipGetLastError();
+}
+
+// the assembly stage (a.tot cleared by the caller)
+hipError_t assemble_stage(const k4_call &c, const k4_pair &cur, rxg_segment *seg,
+                          rxg_tcp_stream *stream, uint8_t *payload, uint64_t cap) {
+    const dim3 grid(c.nblk), block(SS_THREADS), one(1), scan(1024);
+    const auto &a = c.w.a;
+    hipLaunchKernelGGL(asm_record_kernel, grid, block, 0, c.s, c.pkts, c.off, c.len, c.unit_log2,
+                       cur.k, cur.v, c.totals, seg, a.dl, a.hl, a.bH, a.bZ);
+    hipLaunchKernelGGL(gro_scan_kernel, dim3(2), scan, 0, c.s, a.bZ, a.bH, c.totals, nullptr);
+    hipLaunchKernelGGL(asm_end_kernel, grid, block, 0, c.s, seg, c.totals, a.dl, a.hl, a.bH, a.av,
+                       a.il, a.bV, a.bF);
+    hipLaunchKernelGGL(asm_scan_kernel, one, scan, 0, c.s, a.bV, a.bF, c.totals);
+    hipLaunchKernelGGL(asm_head_kernel, grid, block, 0, c.s, seg, c.totals, a.dl, a.hl, a.av, a.il,
+                       a.bV, a.tk, a.s32, a.fl, a.sl, a.tl, a.bR, a.bT);
+    hipLaunchKernelGGL(gro_scan_kernel, one, scan, 0, c.s, a.bT, nullptr, c.totals, a.tot);
+    hipLaunchKernelGGL(gro_scan_kernel, one, scan, 0, c.s, a.bR, nullptr, c.totals, a.tot + 1);
+    hipLaunchKernelGGL(asm_streamid_kernel, grid, block, 0, c.s, c.totals, a.tot, a.fl, a.sl, a.bR,
+                       a.sfirst);
+    hipLaunchKernelGGL(asm_stream_kernel, grid, block, 0, c.s, seg, c.totals, a.tot, a.tl, a.bT, a.s32,
+                       a.fl, a.sfirst, stream, a.ol, a.bO);
+    hipLaunchKernelGGL(gro_scan_kernel, one, scan, 0, c.s, a.bO, nullptr,
+                       reinterpret_cast<const uint32_t *>(a.tot + 1), a.tot + 2);
+    hipLaunchKernelGGL(asm_copy_kernel, ss_copy_grid(c.n), block, 0, c.s, c.pkts, c.off, c.len,
+                       c.unit_log2, a.tot, a.dl, a.tk, a.tl, a.bT, a.sl, a.sfirst, a.ol, a.bO, seg,
+                       stream, payload, cap, c.totals);
+    return hipGetLastError();
+}
+
+// the call on a burst of n > 0 frames, its workspace carved
+k4_call k4_begin(const uint8_t *pkts, const uint32_t *off, const uint16_t *len, uint32_t n,
+                 uint32_t unit_log2, const uint4 *verd, uint32_t nt, uint32_t *totals, void *ws,
+                 hipStream_t s) {
+    return {pkts, off, len, n, unit_log2, verd, nt, totals, s, ss_tiles(n), ss_blocks(n), k4_carve(ws, n)};
+}
+
+} // namespace
+
+size_t rx_segsort_ws_bytes(uint32_t n) { return k4_carve(nullptr, n).end_sort; }
+size_t rx_gro_ws_bytes(uint32_t n) { return k4_carve(nullptr, n).end_gro; }
+size_t rx_order_ws_bytes(uint32_t n) { return k4_carve(nullptr, n).end_order; }
+size_t rx_assemble_ws_bytes(uint32_t n) { return k4_carve(nullptr, n).end_assemble; }
+
+// K4: the sort and the record stage; d_totals: 3 (segments, payload bytes,
+// overflow flag)
+hipError_t rx_segsort_launch(const uint8_t *pkts, const uint32_t *off, const uint16_t *len,
+                             uint32_t n, uint32_t unit_log2, const uint4 *verd, uint32_t nt,
+                             rxg_segment *seg, uint8_t *payload, uint64_t cap, uint32_t *totals,
+                             void *ws, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(totals, 0, 3 * sizeof(uint32_t), s);
+    if (e != hipSuccess || n == 0 || nt == 0) return e;
+    const k4_call c = k4_begin(pkts, off, len, n, unit_log2, verd, nt, totals, ws, s);
+    k4_pair cur, spare;
+    if ((e = sort_stage(c, cur, spare)) != hipSuccess) return e;
+    return record_stage(c, cur, seg, payload, cap);
+}
+
+// the sort and the coalescing stage; d_totals: 4 (segments, payload bytes,
+// overflow flag, runs)
+hipError_t rx_gro_launch(const uint8_t *pkts, const uint32_t *off, const uint16_t *len, uint32_t n,
+                         uint32_t unit_log2, const uint4 *verd, uint32_t nt, uint32_t W,
+                         rxg_segment *seg, rxg_tcp_run *run, uint8_t *payload, uint64_t cap,
+                         uint32_t *totals, void *ws, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(totals, 0, 4 * sizeof(uint32_t), s);
+    if (e != hipSuccess || n == 0 || nt == 0) return e;
+    const k4_call c = k4_begin(pkts, off, len, n, unit_log2, verd, nt, totals, ws, s);
+    k4_pair cur, spare;
+    if ((e = hipMemsetAsync(c.w.g.tot, 0, 3 * sizeof(uint64_t), s)) != hipSuccess) return e;
+    if ((e = sort_stage(c, cur, spare)) != hipSuccess) return e;
+    return coalesce_stage(c, cur, W, seg, run, payload, cap);
+}
+
+// the sort, the ordering stage, then K4's record stage (W == 0; payload NULL:
+// records only) or the coalescing stage (W != 0); d_totals: 5 (segments,
+// payload bytes, overflow flag, runs, moved)
+hipError_t rx_order_launch(const uint8_t *pkts, const uint32_t *off, const uint16_t *len, uint32_t n,
+                           uint32_t unit_log2, const uint4 *verd, uint32_t nt, uint32_t W,
+                           rxg_segment *seg, rxg_tcp_run *run, uint8_t *payload, uint64_t cap,
+                           uint32_t *totals, void *ws, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(totals, 0, 5 * sizeof(uint32_t), s);
+    if (e != hipSuccess || n == 0 || nt == 0) return e;
+    const k4_call c = k4_begin(pkts, off, len, n, unit_log2, verd, nt, totals, ws, s);
+    k4_pair cur, spare;
+    if ((e = hipMemsetAsync(c.w.o.flag, 0, sizeof(uint32_t), s)) != hipSuccess) return e;
+    if ((e = sort_stage(c, cur, spare)) != hipSuccess) return e;
+    if ((e = order_stage(c, cur, spare)) != hipSuccess) return e;
+    if (!W) return record_stage(c, cur, seg, payload, cap);
+    if ((e = hipMemsetAsync(c.w.g.tot, 0, 3 * sizeof(uint64_t), s)) != hipSuccess) return e;
+    return coalesce_stage(c, cur, W, seg, run, payload, cap);
+}
+
+// the sort, the ordering stage and the assembly stage; d_totals: 6 (segments,
 // payload bytes, overflow flag, streams, moved, sum of skip)
 hipError_t rx_assemble_launch(const uint8_t *pkts, const uint32_t *off, const uint16_t *len,
                               uint32_t n, uint32_t unit_log2, const uint4 *verd, uint32_t nt,
@@ -1438,114 +1397,11 @@ hipError_t rx_assemble_launch(const uint8_t *pkts, const uint32_t *off, const ui
                               uint64_t cap, uint32_t *totals, void *ws, hipStream_t s) {
     hipError_t e = hipMemsetAsync(totals, 0, 6 * sizeof(uint32_t), s);
     if (e != hipSuccess || n == 0 || nt == 0) return e;
-    const size_t nn = ss_align((size_t)n * 4);
-    uint8_t *w8 = static_cast<uint8_t *>(ws);
-    uint32_t *ka = reinterpret_cast<uint32_t *>(w8), *va = reinterpret_cast<uint32_t *>(w8 + nn);
-    uint32_t *kb = reinterpret_cast<uint32_t *>(w8 + 2 * nn), *vb = reinterpret_cast<uint32_t *>(w8 + 3 * nn);
-    const uint32_t ntiles = ss_tiles(n), nblk = ss_blocks(n);
-    uint32_t *hist = reinterpret_cast<uint32_t *>(w8 + 4 * nn);
-    const size_t nb8 = ss_align((size_t)nblk * 8);
-    uint8_t *o8 = w8 + rx_gro_ws_bytes(n);
-    uint32_t *sq = reinterpret_cast<uint32_t *>(o8), *ohl = reinterpret_cast<uint32_t *>(o8 + nn);
-    uint32_t *hk = reinterpret_cast<uint32_t *>(o8 + 2 * nn);
-    uint32_t *oka = reinterpret_cast<uint32_t *>(o8 + 3 * nn), *pa = reinterpret_cast<uint32_t *>(o8 + 4 * nn);
-    uint32_t *okb = reinterpret_cast<uint32_t *>(o8 + 5 * nn), *pb = reinterpret_cast<uint32_t *>(o8 + 6 * nn);
-    uint64_t *obH = reinterpret_cast<uint64_t *>(o8 + 7 * nn);
-    uint64_t *obZ = reinterpret_cast<uint64_t *>(o8 + 7 * nn + nb8);
-    uint32_t *flag = reinterpret_cast<uint32_t *>(o8 + 7 * nn + 2 * nb8);
-    uint8_t *a8 = w8 + rx_order_ws_bytes(n);
-    uint32_t *dl = reinterpret_cast<uint32_t *>(a8), *hl = reinterpret_cast<uint32_t *>(a8 + nn);
-    uint32_t *av = reinterpret_cast<uint32_t *>(a8 + 2 * nn), *tk = reinterpret_cast<uint32_t *>(a8 + 3 * nn);
-    uint32_t *s32 = reinterpret_cast<uint32_t *>(a8 + 4 * nn), *fl = reinterpret_cast<uint32_t *>(a8 + 5 * nn);
-    uint32_t *sl = reinterpret_cast<uint32_t *>(a8 + 6 * nn);
-    uint32_t *sfirst = reinterpret_cast<uint32_t *>(a8 + 7 * nn);
-    uint32_t *ol = reinterpret_cast<uint32_t *>(a8 + 8 * nn), *tl = reinterpret_cast<uint32_t *>(a8 + 9 * nn);
-    const size_t n8 = ss_align((size_t)n * 8);
-    uint64_t *il = reinterpret_cast<uint64_t *>(a8 + 10 * nn);
-    uint8_t *b8 = a8 + 10 * nn + n8;
-    uint64_t *bH = reinterpret_cast<uint64_t *>(b8), *bZ = reinterpret_cast<uint64_t *>(b8 + nb8);
-    uint64_t *bV = reinterpret_cast<uint64_t *>(b8 + 2 * nb8), *bF = reinterpret_cast<uint64_t *>(b8 + 3 * nb8);
-    uint64_t *bR = reinterpret_cast<uint64_t *>(b8 + 4 * nb8), *bT = reinterpret_cast<uint64_t *>(b8 + 5 * nb8);
-    uint64_t *bO = reinterpret_cast<uint64_t *>(b8 + 6 * nb8);
-    uint64_t *tot = reinterpret_cast<uint64_t *>(b8 + 7 * nb8); // {sum of take, streams, bytes used}
-    if ((e = hipMemsetAsync(flag, 0, sizeof(uint32_t), s)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(tot, 0, 3 * sizeof(uint64_t), s)) != hipSuccess) return e;
-    // one stable radix pass of K4's sort over digit `shift` of (ki, vi)
-    auto pass = [&](const uint32_t *ki, const uint32_t *vi, uint32_t shift, uint32_t *ko,
-                    uint32_t *vo) -> hipError_t {
-        hipLaunchKernelGGL(ss_hist_kernel<false>, dim3(ntiles), dim3(SS_THREADS), 0, s, verd, ki, n,
-                           nt, shift, ntiles, hist, totals);
-        hipLaunchKernelGGL(ss_scan_kernel, dim3(1), dim3(1024), 0, s, hist, SS_DIGITS * ntiles,
-                           nullptr);
-        hipLaunchKernelGGL(ss_scatter_kernel<false>, dim3(ntiles), dim3(SS_THREADS), 0, s, verd, ki,
-                           vi, n, nt, shift, ntiles, hist, ko, vo);
-        return hipGetLastError();
-    };
-    // the sort, as in rx_segsort_launch
-    const uint32_t bits = 32u - (uint32_t)__builtin_clz(nt);
-    const uint32_t passes = (bits + 7u) / 8u;
-    const uint32_t *kin = nullptr, *vin = nullptr;
-    uint32_t *kout = ka, *vout = va;
-    for (uint32_t p = 0; p < passes; ++p) {
-        const uint32_t shift = 8u * p;
-        if (p == 0) {
-            hipLaunchKernelGGL(ss_hist_kernel<true>, dim3(ntiles), dim3(SS_THREADS), 0, s, verd,
-                               nullptr, n, nt, shift, ntiles, hist, totals);
-            hipLaunchKernelGGL(ss_scan_kernel, dim3(1), dim3(1024), 0, s, hist, SS_DIGITS * ntiles,
-                               nullptr);
-            hipLaunchKernelGGL(ss_scatter_kernel<true>, dim3(ntiles), dim3(SS_THREADS), 0, s, verd,
-                               nullptr, nullptr, n, nt, shift, ntiles, hist, kout, vout);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-        } else if ((e = pass(kin, vin, shift, kout, vout)) != hipSuccess) {
-            return e;
-        }
-        kin = kout, vin = vout;
-        kout = (kout == ka) ? kb : ka;
-        vout = (vout == va) ? vb : va;
-    }
-    // the permutation, as in rx_order_launch
-    hipLaunchKernelGGL(ord_head_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, pkts, off, len, unit_log2,
-                       kin, vin, totals, sq, ohl, obH, obZ);
-    hipLaunchKernelGGL(gro_scan_kernel, dim3(2), dim3(1024), 0, s, obZ, obH, totals, nullptr);
-    hipLaunchKernelGGL(ord_key_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, totals, n, sq, ohl, obH,
-                       oka, hk, pa, flag);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    uint32_t *ok = oka, *pv = pa, *ok2 = okb, *pv2 = pb;
-    for (uint32_t p = 0; p < 4u; ++p) {
-        if ((e = pass(ok, pv, 8u * p, ok2, pv2)) != hipSuccess) return e;
-        uint32_t *x = ok; ok = ok2, ok2 = x;
-        x = pv, pv = pv2, pv2 = x;
-    }
-    hipLaunchKernelGGL(ord_headkey_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, n, flag, hk, pv, ok);
-    const uint32_t hbits = n > 1u ? 32u - (uint32_t)__builtin_clz(n - 1u) : 1u;
-    for (uint32_t p = 0; p < (hbits + 7u) / 8u; ++p) {
-        if ((e = pass(ok, pv, 8u * p, ok2, pv2)) != hipSuccess) return e;
-        uint32_t *x = ok; ok = ok2, ok2 = x;
-        x = pv, pv = pv2, pv2 = x;
-    }
-    hipLaunchKernelGGL(ord_apply_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, n, flag, pv, kin, vin,
-                       kout, vout, totals);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    kin = kout, vin = vout;
-    // the assembly
-    hipLaunchKernelGGL(asm_record_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, pkts, off, len,
-                       unit_log2, kin, vin, totals, seg, dl, hl, bH, bZ);
-    hipLaunchKernelGGL(gro_scan_kernel, dim3(2), dim3(1024), 0, s, bZ, bH, totals, nullptr);
-    hipLaunchKernelGGL(asm_end_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, seg, totals, dl, hl, bH,
-                       av, il, bV, bF);
-    hipLaunchKernelGGL(asm_scan_kernel, dim3(1), dim3(1024), 0, s, bV, bF, totals);
-    hipLaunchKernelGGL(asm_head_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, seg, totals, dl, hl, av,
-                       il, bV, tk, s32, fl, sl, tl, bR, bT);
-    hipLaunchKernelGGL(gro_scan_kernel, dim3(1), dim3(1024), 0, s, bT, nullptr, totals, tot);
-    hipLaunchKernelGGL(gro_scan_kernel, dim3(1), dim3(1024), 0, s, bR, nullptr, totals, tot + 1);
-    hipLaunchKernelGGL(asm_streamid_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, totals, tot, fl, sl,
-                       bR, sfirst);
-    hipLaunchKernelGGL(asm_stream_kernel, dim3(nblk), dim3(SS_THREADS), 0, s, seg, totals, tot, tl,
-                       bT, s32, fl, sfirst, stream, ol, bO);
-    hipLaunchKernelGGL(gro_scan_kernel, dim3(1), dim3(1024), 0, s, bO, nullptr,
-                       reinterpret_cast<const uint32_t *>(tot + 1), tot + 2);
-    hipLaunchKernelGGL(asm_copy_kernel, dim3((uint32_t)(((uint64_t)n + 3) / 4)), dim3(SS_THREADS), 0,
-                       s, pkts, off, len, unit_log2, tot, dl, tk, tl, bT, sl, sfirst, ol, bO, seg,
-                       stream, payload, cap, totals);
-    return hipGetLastError();
+    const k4_call c = k4_begin(pkts, off, len, n, unit_log2, verd, nt, totals, ws, s);
+    k4_pair cur, spare;
+    if ((e = hipMemsetAsync(c.w.o.flag, 0, sizeof(uint32_t), s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(c.w.a.tot, 0, 3 * sizeof(uint64_t), s)) != hipSuccess) return e;
+    if ((e = sort_stage(c, cur, spare)) != hipSuccess) return e;
+    if ((e = order_stage(c, cur, spare)) != hipSuccess) return e;
+    return assemble_stage(c, cur, seg, stream, payload, cap);
 }

@@ -139,6 +139,49 @@ def rule_cases(rng, dport=9999, base=0):
     return out
 
 
+# (frames = records, id space) at the edges of the device stages: one record
+# block of 256 and one sort tile of 2048, and one past each; 255 | 256 ids: the
+# flow sort's one and two radix passes; 256 | 257 positions: the ordering
+# stage's head-index sort likewise
+STAGE_EDGES = [(1, 255), (255, 256), (256, 255), (257, 256), (2049, 255)]
+
+
+def boundary_burst(n, nconn, seed, cut=False):
+    """(frames, caps, forced) of n frames, every one a delivered segment of
+    connections conn(0 .. nconn - 1), for the edges of the device stages (the
+    callers choose n = the record count and nconn + 1 = the id space).
+    Connection 0 takes all but four: in sequence, payloads of 33, 34, 35, 36, 17
+    and 1 B (a chain's copies start at every byte phase of source and
+    destination), every 7th overlapping its predecessor by 1 to 3 B (the
+    assembly's skip shifts the source phase as well), every 11th with hl = 6,
+    neighbours swapped here and there (something to order).  Connections 1 and
+    nconn - 1 (the top id) take two each.  cut: connection 1's second capture
+    ends at byte 40, inside the TCP header: seq's low half, ack, hl and flags
+    read 0; K1 would not deliver it, so forced = {its index: 1} is the verdict
+    to give it."""
+    rng = np.random.default_rng(seed)
+    frames, seq = [], 2 ** 32 - 3000
+    for q in range(n - 4 if n > 4 else n):
+        ln = (33, 34, 35, 36, 17, 1)[q % 6]
+        if q % 7 == 6:
+            seq -= 1 + q % 3
+        frames.append(F.tcp_frame(*conn(0), L, 9999, _p(rng, ln), seq=seq & 0xFFFFFFFF,
+                                  **({"data_off": 0x60} if q % 11 == 10 else {})))
+        seq += ln
+    for q in range(0, len(frames) - 1, 5):
+        frames[q], frames[q + 1] = frames[q + 1], frames[q]
+    if n > 4:
+        for k in (1, nconn - 1):
+            at = int(rng.integers(0, len(frames)))
+            frames[at:at] = [F.tcp_frame(*conn(k), L, 9999, _p(rng, 40), seq=70000 + 40 * q) for q in (1, 0)]
+    assert len(frames) == n
+    caps, forced = [len(f) for f in frames], {}
+    if cut and n > 4:
+        i = max(j for j, f in enumerate(frames) if f[34:36] == (40001).to_bytes(2, "big"))
+        caps[i], forced = 40, {i: 1}
+    return frames, caps, forced
+
+
 # ---- the socket layer against the oracle ----------------------------------------
 def _client_script(rng, k, dport):
     """one client's segments in order: handshake, trains of 1 to 9 in-sequence

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import frames as F
+import gro_ref as G
 import oracle_bind as O
 import rxgpu as R
 
@@ -261,6 +262,53 @@ def test_tcp_segment_sort_matches_model(torch_dev, ntcb, passes):
     assert np.all(pl[len(want_pl):] == 0xCD)  # nothing written past the used bytes
     assert any(s["plen"] < 0 for s in want_seg) and any((s["flags"] & 0x09) == 0x09
                                                          for s in want_seg)
+
+
+@pytest.mark.parametrize("n,ids", G.STAGE_EDGES)
+def test_tcp_segment_sort_stage_edges(torch_dev, n, ids):
+    """K4, with its payload buffer and records only, at the record counts and id
+    spaces where its stages take another path (gro_ref.STAGE_EDGES), on a burst
+    with one capture cut inside the TCP header; the verdicts are the oracle's,
+    the cut capture's forced (K1 would not deliver it)"""
+    torch, dev = torch_dev
+    frames, caps, forced = G.boundary_burst(n, ids - 1, 11, cut=True)
+    tcb = np.zeros(ids, R.TCB_DTYPE)
+    for k in range(ids - 1):
+        cip, cport = G.conn(k)
+        tcb[k] = (R.ip_raw(cip), R.ip_raw(L), R.port_raw(cport), R.port_raw(9999), 4)
+    tcb[ids - 1] = (0, R.ip_raw(L), 0, R.port_raw(9999), R.TCP_STATUS_LISTEN)
+    buf, off, lens = F.pack_frames(frames, 6, caplens=caps)
+    v = O.Tables(np.zeros(0, R.UDP_SOCK_DTYPE), tcb).classify(buf, off, lens, 6)
+    for i, fid in forced.items():
+        v[i]["flow_id"], v[i]["cls"], v[i]["rc"] = fid, R.CLS_TCP, 0
+    want_seg, want_pl = _seg_model(buf, off, lens, v, ids)
+    assert len(want_seg) == n and (n == 1 or any(s["hl"] == 0 for s in want_seg))
+    with R.Context(0) as ctx:
+        ctx.flows_sync(None, tcb)
+        d_pk = torch.from_numpy(np.concatenate([buf, np.zeros(64, np.uint8)])).to(dev)
+        d_off = torch.from_numpy(off.view(np.int32)).to(dev)
+        d_ln = torch.from_numpy(lens.view(np.int16)).to(dev)
+        d_v = torch.from_numpy(np.frombuffer(v.tobytes(), np.uint8).copy()).to(dev)
+        sh = torch.cuda.current_stream(dev).cuda_stream
+        cap = len(buf) + 4096
+        for payload in (True, False):
+            d_seg = torch.full((n * 32,), 0xEE, dtype=torch.uint8, device=dev)
+            d_pl = torch.full((cap,), 0xCD, dtype=torch.uint8, device=dev)
+            d_tot = torch.full((3,), 7, dtype=torch.int32, device=dev)
+            ctx.tcp_compact_dev(d_pk, d_off, d_ln, n, 6, d_v, d_seg, d_pl if payload else None, cap,
+                                d_tot, stream=sh)
+            torch.cuda.synchronize(dev)
+            tot = d_tot.cpu().numpy().view(np.uint32)
+            seg = d_seg.cpu().numpy().view(R.SEGMENT_DTYPE)
+            pl = d_pl.cpu().numpy()
+            want = want_seg.copy()
+            if not payload:
+                want["offset"] = 34 + 4 * want["hl"].astype(np.uint32)
+            assert list(tot) == [n, len(want_pl) if payload else 0, 0]
+            bad = [k for k in range(n) if seg[k].tobytes() != want[k].tobytes()]
+            assert not bad, [(k, seg[k], want[k]) for k in bad[:5]]
+            used = len(want_pl) if payload else 0
+            assert pl[:used].tobytes() == want_pl[:used] and np.all(pl[used:] == 0xCD)
 
 
 def test_tcp_segment_sort_edge_bursts(torch_dev):

@@ -81,12 +81,15 @@ def _shuffle_within(rng, per):
     return frames
 
 
-def _run(torch, dev, ctx, frames, caps, unit, cap=None):
+def _run(torch, dev, ctx, frames, caps, unit, cap=None, forced=None):
     """the device call on one burst, every output pre-filled; returns the
-    outputs beside what the model and the host restatement say"""
+    outputs beside what the model and the host restatement say.  forced:
+    {frame: tcb id} of frames to deliver whatever the oracle's verdict"""
     n = len(frames)
     buf, off, lens = F.pack_frames(frames, unit, caplens=caps)
     v = O.Tables(np.zeros(0, R.UDP_SOCK_DTYPE), ctx._tcb).classify(buf, off, lens, unit)
+    for i, fid in (forced or {}).items():
+        v[i]["flow_id"], v[i]["cls"], v[i]["rc"] = fid, R.CLS_TCP, 0
     flows = [int(x["flow_id"]) if x["cls"] == R.CLS_TCP and x["rc"] == 0 and
              x["flow_id"] < len(ctx._tcb) else None for x in v]
     seg0, sip0 = G.records(frames, caps, flows)
@@ -229,6 +232,25 @@ def test_assemble_one_connection_across_the_block_edges(torch_dev):
     assert list(st["first"]) == [0, 254, 257, 510, 514] and list(st["flags"]) == [0, 2, 2, 2, 2]
     assert all(m["take"][i] == 0 and m["skip"][i] > 0 for i in (250, 255, 256, 300, 511, 512))
     assert np.count_nonzero(m["take"] == 0) == 6
+
+
+@pytest.mark.parametrize("n,ids", G.STAGE_EDGES)
+def test_assemble_stage_edges(torch_dev, n, ids):
+    """the record counts and id spaces where the sort, the ordering stage and
+    the assembly stage take another path (gro_ref.STAGE_EDGES), on a burst with
+    one capture cut inside the TCP header; the 16-B chunks are read from every
+    byte phase of the source (the overlaps' skip shifts it)"""
+    torch, dev = torch_dev
+    frames, caps, forced = G.boundary_burst(n, ids - 1, 55, cut=True)
+    with _Ctx(_tcbs(ids - 1)) as ctx:
+        wseg, m, pl, tot = _run(torch, dev, ctx, frames, caps, 6, forced=forced)
+    assert len(wseg) == n and (n == 1 or np.count_nonzero(wseg["hl"] == 0) == 1)
+    if n > 4:
+        assert tot[4] > 0 and tot[5] > 0                               # moved, skipped
+        hlen = (16 - m["dst"].astype(np.int64) % 16) % 16              # bytes before the first 16-B chunk
+        chunk = m["take"] >= hlen + 16
+        src = 34 + 4 * wseg["hl"].astype(np.int64) + m["skip"] + hlen
+        assert {int(x) for x in src[chunk] % 4} == {0, 1, 2, 3}
 
 
 def test_assemble_600_groups(torch_dev):

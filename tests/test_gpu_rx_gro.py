@@ -192,6 +192,23 @@ def test_coalesce_matches_model_compact_and_frames(torch_dev, unit):
         _coalesce(torch, dev, ctx, frames, caps, unit, 65536, short=True)
 
 
+@pytest.mark.parametrize("n,ids", G.STAGE_EDGES)
+def test_coalesce_stage_edges(torch_dev, n, ids):
+    """the record counts and id spaces where the sort and the coalescing stage
+    take another path (gro_ref.STAGE_EDGES); the chain's 16-B chunks are read
+    from every byte phase of the source"""
+    torch, dev = torch_dev
+    frames, caps, _ = G.boundary_burst(n, ids - 1, 7)
+    with _Ctx(_tcbs(ids - 1)) as ctx:
+        for W in (1460, 65536):
+            seg, run = _coalesce(torch, dev, ctx, frames, caps, 6, W)
+    assert len(seg) == n
+    if n > 4:
+        hlen = (16 - seg["offset"].astype(np.int64) % 16) % 16     # bytes before the first 16-B chunk
+        chunk = seg["ncopy"] >= hlen + 16
+        assert {int(x) for x in (34 + 4 * seg["hl"][chunk] + hlen[chunk]) % 4} == {0, 1, 2, 3}
+
+
 def test_coalesce_single_flow_burst(torch_dev):
     torch, dev = torch_dev
     frames, caps, tcb = _single_flow_burst()

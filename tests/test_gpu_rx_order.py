@@ -302,6 +302,19 @@ def test_ordered_group_across_the_tile_boundary(torch_dev):
     assert np.count_nonzero(perm[:1900] != np.arange(1900)) > 1800
 
 
+@pytest.mark.parametrize("n,ids", G.STAGE_EDGES)
+def test_ordered_stage_edges(torch_dev, n, ids):
+    """the record counts and id spaces where the sort, the ordering stage, K4's
+    record stage and the coalescing stage take another path
+    (gro_ref.STAGE_EDGES), on a burst with one capture cut inside the TCP
+    header"""
+    torch, dev = torch_dev
+    burst = G.boundary_burst(n, ids - 1, 34, cut=True)
+    with _Ctx(_tcbs(ids - 1)) as ctx:
+        wseg, perm = _check_burst(torch, dev, ctx, burst, 6, windows=(0, 65536), want_moved=n > 4)
+    assert len(wseg) == n and (n == 1 or np.count_nonzero(wseg["hl"] == 0) == 1)
+
+
 def test_ordered_one_connection_owns_the_burst_reversed(torch_dev):
     torch, dev = torch_dev
     burst = _single_flow_burst()
