@@ -410,8 +410,7 @@ RX_HD uint32_t rx_build_header(const rxg_gen_cfg &cfg, uint64_t i, const rx_fram
     {
         uint32_t s = 0;
         for (uint32_t q = 14; q < 34; q += 2) s += rx_get16le(h, q);
-        uint32_t c = rx_fold(s);
-        c = (c == 0xFFFFu) ? c : (~c & 0xFFFFu);
+        uint32_t c = ~rx_fold(s) & 0xFFFFu; // plain complement, as the reference's build
         rx_put16le(h, 24, c);
     }
     uint32_t hdr_len, hole;

@@ -87,8 +87,9 @@ __device__ __forceinline__ void tx_frame(uint8_t *fb, int32_t cp, bool valid, co
     ip = gsum<G>(ip); // group totals in every lane of the group
     acc = gsum<G>(acc);
     if (!valid || !ipv4) return;
-    const uint32_t kip = fold16(ip); // rte_ipv4_cksum, rte_ip.h:255-265
-    const uint32_t hip = kip == 0xFFFFu ? kip : (~kip & 0xFFFFu);
+    // rte_ipv4_cksum as compiled into the reference (DPDK 19.11.12): the plain
+    // complement, so a header summing to 0xFFFF stores 0 (no 0xFFFF rule yet)
+    const uint32_t hip = ~fold16(ip) & 0xFFFFu;
     acc += (proto << 8) + rx_bswap16(l4n); // pseudo-header {0, proto}, be16(l4 len)
     uint32_t kl4 = (~fold16(acc)) & 0xFFFFu; // rte_ipv4_udptcp_cksum, rte_ip.h:325-349
     if (kl4 == 0u && proto == 17u) kl4 = 0xFFFFu;

@@ -390,8 +390,9 @@ __device__ __forceinline__ void txe_frame_run(const txe_frame &f, uint4 d0, uint
     if (f.nb == 0) return;
     if (ipv4 && !no_cksum) {
         const uint32_t l4n = fl - 34u;
-        const uint32_t kip = fold16(ip); // rte_ipv4_cksum, rte_ip.h:255-265
-        const uint32_t hip = kip == 0xFFFFu ? kip : (~kip & 0xFFFFu);
+        // rte_ipv4_cksum as compiled into the reference: the plain complement
+        // (a header summing to 0xFFFF stores 0), see tx_cksum.hip
+        const uint32_t hip = ~fold16(ip) & 0xFFFFu;
         acc += (proto << 8) + rx_bswap16(l4n); // pseudo-header {0, proto}, be16(l4 len)
         uint32_t kl4 = (~fold16(acc)) & 0xFFFFu; // rte_ipv4_udptcp_cksum, rte_ip.h:325-349
         if (kl4 == 0u && proto == 17u) kl4 = 0xFFFFu;

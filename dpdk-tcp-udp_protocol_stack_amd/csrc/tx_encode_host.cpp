@@ -108,7 +108,7 @@ void encode(uint8_t *m, const rxg_txd &d, uint32_t fl, const uint8_t *pay) {
 
 void fill_cksums(uint8_t *m, uint32_t fl, bool tcp) {
     const uint32_t kip = fold16(raw_sum(m + 14, 20, 0));
-    const uint16_t hip = (uint16_t)(kip == 0xFFFFu ? kip : ~kip);
+    const uint16_t hip = (uint16_t)~kip; // plain complement: 0xFFFF stores 0, as the reference's build
     const uint32_t l4n = fl - 34;
     // pseudo-header: sip, dip, {0, proto}, be16(l4 length)
     uint32_t s = raw_sum(m + 26, 8, 0) + ((tcp ? 6u : 17u) << 8) +

@@ -906,8 +906,9 @@ int rxg_tx_cksum(rxg_ctx *ctx, uint8_t *pkts, uint64_t span_bytes, const uint32_
  *   RXG_TXD_TCP  ng_encode_tcp_apppkt tcp.c:420-466   54 + 4*optlen + pay_len
  *   RXG_TXD_ARP  ng_encode_arp_pkt    common.c:206-241 42 (request, opcode 1)
  * IPv4 id and fragment fields 0, ttl 64 (udp.c:74-85, tcp.c:434-445); the
- * IPv4 header checksum (rte_ipv4_cksum, 0xFFFF kept) at offset 24 and the L4
- * checksum (rte_ipv4_udptcp_cksum, UDP 0 -> 0xFFFF) at 40 / 50 are those
+ * IPv4 header checksum (rte_ipv4_cksum: the plain complement, so a sum of
+ * 0xFFFF stores 0) at offset 24 and the L4 checksum
+ * (rte_ipv4_udptcp_cksum, UDP 0 -> 0xFFFF) at 40 / 50 are those
  * rxg_tx_cksum fills; every frame is zero-filled to its next 64-B boundary.
  * The descriptor is 48 bytes, 16-B aligned (offsets in the comments). */
 enum { RXG_TXD_UDP = 0, RXG_TXD_TCP = 1, RXG_TXD_ARP = 2 };

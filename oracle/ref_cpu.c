@@ -21,19 +21,20 @@
  *     rte_ipv4_phdr_cksum    rte_ip.h:288-309
  *     rte_ipv4_udptcp_cksum  rte_ip.h:325-349
  *
- * Parity pin: the reference cannot be built here (tcp.c holds unresolved
- * merge-conflict hunks and DPDK headers are absent) and its prebuilt
- * objects (build/ *.o files) are vendored machine code that this project never
- * runs or loads.  The reference ships no tests or fixtures.  This
- * restatement is therefore pinned by (1) the known-answer values SURVEY.md
- * §8(a) records from the reference's compiled code, (2) RFC 1071 §3's
- * published example, (3) the published Microsoft RSS verification vectors
- * (for the RSS hash only).  See tests/golden/ and DESIGN.md §Oracle.
+ * Parity pin: the reference's sources cannot be built here (tcp.c holds
+ * unresolved merge-conflict hunks and DPDK headers are absent), but its
+ * prebuilt objects link and run: oracle/_ref/refrun (refrun_main.c,
+ * refrun_stubs.c; built where the objects exist, never committed) runs them,
+ * tests/test_ref_differential.py compares this restatement with them exactly,
+ * and tests/golden/ref_* records their answers for machines without them.
+ * Beside that: the known-answer values of SURVEY.md §8(a), RFC 1071 §3's
+ * example and the Microsoft RSS verification vectors (for the RSS hash only).
+ * See tests/golden/ and DESIGN.md §2 (also for what stays unpinned).
  *
  * Frames shorter than what the reference would read (caplen < bytes it
  * touches) are evaluated on a zero-extended copy and flagged RXG_F_TRUNC:
- * the reference reads adjacent memory there, so parity is defined, not
- * inherited, for those bytes.
+ * the reference reads adjacent memory there; refrun lays every frame into a
+ * zeroed buffer, so the reference's answer under this rule is known too.
  */
 #include "ref_cpu.h"
 
@@ -96,10 +97,13 @@ uint16_t oracle_raw_cksum(const void *buf, uint32_t len) {
 }
 
 /* rte_ipv4_cksum, rte_ip.h:255-265 (TX only in the reference; used by the
- * tests to build well-formed frames) */
+ * tests to build well-formed frames).  As compiled into the reference's
+ * udp.o it is the plain complement: a header whose sum is 0xFFFF stores 0.
+ * (Later DPDK releases keep 0xFFFF there; 19.11.12 does not, and
+ * tests/test_ref_differential.py holds this to the compiled code.) */
 uint16_t oracle_ipv4_cksum(const uint8_t *ipv4_hdr) {
     uint16_t c = oracle_raw_cksum(ipv4_hdr, 20);
-    return (uint16_t)((c == 0xffff) ? c : ~c);
+    return (uint16_t)~c;
 }
 
 /* rte_ipv4_phdr_cksum, rte_ip.h:288-309 with ol_flags = 0:

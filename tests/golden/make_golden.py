@@ -5,7 +5,9 @@
    literals, never computed here:
      * "survey"  : values SURVEY.md §8(a) ("Known-answer edge cases", lines
                    295-307) records from the reference's own compiled
-                   rte_ipv4_udptcp_cksum / udp_process / tcp_process;
+                   rte_ipv4_udptcp_cksum / udp_process / tcp_process
+                   (tests/test_ref_differential.py asks that code again for
+                   each of them where it is present);
      * "rfc1071" : RFC 1071 §3 numerical example;
      * "ms_rss"  : Microsoft "Verifying the RSS Hash Calculation" IPv4 table
                    (standard 40-byte key).
@@ -13,9 +15,11 @@
 2. edge.pcap + edge_flows.npz + edge_verdicts.npy — a regression fixture of
    edge-case frames (truncation, IHL, negative TCP payload, short UDP,
    duplicates, listeners, ARP/ICMP/VLAN).  Its verdicts are produced by the
-   oracle (oracle/ref_cpu.c) and are labelled "oracle-derived": they pin the
-   GPU path and future oracle edits to today's restatement, not to the
-   reference (which cannot be run here).
+   oracle (oracle/ref_cpu.c) and are labelled "oracle-derived": a regression
+   fixture for the GPU path and for oracle edits.  The pin to the reference is
+   elsewhere: the same frames go through the reference's own compiled code in
+   tests/test_ref_differential.py, and make_ref_golden.py records that code's
+   answers in ref_rx.pcap / ref_rx_expect.npy.
 
 Run from the repo root:  python tests/golden/make_golden.py
 """
