@@ -96,6 +96,12 @@ hipError_t rx_assemble_launch(const uint8_t *pkts, const uint32_t *off, const ui
                               uint32_t n, uint32_t unit_log2, const uint4 *verd, uint32_t nt,
                               rxg_segment *seg, rxg_tcp_stream *stream, uint8_t *payload,
                               uint64_t cap, uint32_t *totals, void *ws, hipStream_t s);
+size_t rx_l2_ws_bytes(uint32_t n);
+size_t rx_l2_ws_ctl_bytes();
+hipError_t rx_l2_launch(const uint8_t *pkts, const uint32_t *off, const uint16_t *len, uint32_t n,
+                        uint32_t unit_log2, const uint4 *verd, const rxg_l2_params *p, uint8_t *status,
+                        uint8_t *out, uint64_t cap_bytes, uint32_t *roff, uint16_t *rlen, uint32_t *rsrc,
+                        uint32_t *totals, void *ws, hipStream_t s);
 size_t rx_syncookie_ws_bytes(uint32_t n);
 hipError_t rx_syncookie_launch(const uint8_t *pkts, const uint32_t *off, const uint16_t *len, uint32_t n,
                                uint32_t unit_log2, const uint4 *verd, const uint32_t *lmask,
@@ -254,6 +260,17 @@ struct rxg_ctx {
     uint8_t *d_ck_status = nullptr;
     rxg_txd *d_ck_txd = nullptr;
     uint32_t *d_ck_totals = nullptr;
+    // the L2 responder (K8, rx_l2.hip): the workspace of every call on this
+    // context; for the delivery bursts (RXG_DLV_L2) the parameters and answer
+    // capacity of rxg_l2_set and the device results
+    void *d_l2_ws = nullptr;
+    size_t d_l2_ws_cap = 0;
+    rxg_l2_params l2_p{};
+    uint64_t l2_cap = 0;
+    uint8_t *d_l2_status = nullptr, *d_l2_out = nullptr;
+    uint64_t d_l2_out_cap = 0;
+    uint32_t *d_l2_roff = nullptr, *d_l2_rsrc = nullptr, *d_l2_totals = nullptr;
+    uint16_t *d_l2_rlen = nullptr;
     rx_ft_dev ft{};
     uint32_t tune_g = 0, tune_p = 0, tune_fpg = 0, tune_pipe = ~0u; // rxg_tune override
     uint32_t tune_bpc = 0; // rxg_tune_grid: resident blocks per CU cap (0 = occupancy)
@@ -349,6 +366,11 @@ struct rxg_ctx {
     struct delivery_set {
         bool on = false, udp = false, tcp = false, gro = false, order = false, ddos = false;
         bool assemble = false;
+        bool l2 = false;               // (rxg_delivery_l2)
+        uint8_t *h_l2_status = nullptr, *h_l2_out = nullptr;
+        uint64_t h_l2_out_cap = 0;
+        uint32_t *h_l2_roff = nullptr, *h_l2_rsrc = nullptr, *h_l2_totals = nullptr;
+        uint16_t *h_l2_rlen = nullptr;
         bool cookie = false;           // (rxg_delivery_cookies)
         uint8_t *h_ck_status = nullptr;
         rxg_txd *h_ck_txd = nullptr;
@@ -842,12 +864,17 @@ void rxg_close(rxg_ctx *c) {
     (void)hipFree(c->d_ck_txd);
     (void)hipFree(c->d_ck_totals);
     if (c->ev_ck) (void)hipEventDestroy(c->ev_ck);
+    for (void *d : {c->d_l2_ws, (void *)c->d_l2_status, (void *)c->d_l2_out, (void *)c->d_l2_roff,
+                    (void *)c->d_l2_rlen, (void *)c->d_l2_rsrc, (void *)c->d_l2_totals})
+        (void)hipFree(d);
     for (rxg_ctx::delivery_set &ds : c->dls) {
         for (void *h : {(void *)ds.h_cp_dg, (void *)ds.h_cp_first, (void *)ds.h_cp_totals,
                         (void *)ds.h_cp_payload, (void *)ds.h_ss_seg, (void *)ds.h_ss_payload,
                         (void *)ds.h_ss_totals, (void *)ds.h_ss_run, (void *)ds.h_ss_stream,
                         (void *)ds.h_ddos, (void *)ds.h_ck_status, (void *)ds.h_ck_txd,
-                        (void *)ds.h_ck_totals})
+                        (void *)ds.h_ck_totals, (void *)ds.h_l2_status, (void *)ds.h_l2_out,
+                        (void *)ds.h_l2_roff, (void *)ds.h_l2_rlen, (void *)ds.h_l2_rsrc,
+                        (void *)ds.h_l2_totals})
             if (h) (void)hipHostFree(h);
         for (hipEvent_t e : ds.tev)
             if (e) (void)hipEventDestroy(e);
@@ -1243,7 +1270,7 @@ int rxg_tune_tables(rxg_ctx *c, uint32_t flags) {
 
 int rxg_tune_deliver(rxg_ctx *c, uint32_t flags) {
     if (!c || (flags & ~(RXG_DLV_TCP_IN_PLACE | RXG_DLV_TCP_GRO | RXG_DLV_TCP_ORDER | RXG_DLV_DDOS |
-                         RXG_DLV_TCP_ASSEMBLE | RXG_DLV_SYNCOOKIE)))
+                         RXG_DLV_TCP_ASSEMBLE | RXG_DLV_SYNCOOKIE | RXG_DLV_L2)))
         return RXG_EINVAL;
     // (payloads that stay in their frames cannot be made contiguous)
     if ((flags & RXG_DLV_TCP_IN_PLACE) && (flags & RXG_DLV_TCP_GRO)) return RXG_EINVAL;
@@ -2111,6 +2138,73 @@ int rxg_delivery_cookies(rxg_ctx *c, const rxg_delivery *d, const uint8_t **stat
     return RXG_OK;
 }
 
+// K8's launches on s; the context's workspace is grown first.  An empty call
+// zeroes the totals without a launch.
+static int l2_impl(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off, const uint16_t *d_len,
+                   uint32_t n, uint32_t off_unit_log2, const uint4 *d_v, const rxg_l2_params *p,
+                   uint8_t *d_status, uint8_t *d_out, uint64_t cap_bytes, uint32_t *d_roff,
+                   uint16_t *d_rlen, uint32_t *d_rsrc, uint32_t *d_totals, hipStream_t s) {
+    if (n == 0) {
+        HIPCHK(hipMemsetAsync(d_totals, 0, 6 * sizeof(uint32_t), s));
+        return RXG_OK;
+    }
+    const size_t ws = rx_l2_ws_bytes(n);
+    if (ws > c->d_l2_ws_cap) { // (its uses are ordered by the caller: freed and grown in stream order)
+        int rc = ensure_dev_async(&c->d_l2_ws, &c->d_l2_ws_cap, ws, s);
+        if (rc) return rc;
+        // (a fresh workspace: its control words start at zero; every call
+        // leaves them so)
+        HIPCHK(hipMemsetAsync(c->d_l2_ws, 0, rx_l2_ws_ctl_bytes(), s));
+    }
+    HIPCHK(rx_l2_launch(d_pkts, d_off, d_len, n, off_unit_log2, d_v, p, d_status, d_out, cap_bytes,
+                        d_roff, d_rlen, d_rsrc, d_totals, c->d_l2_ws, s));
+    return RXG_OK;
+}
+
+int rxg_l2_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off, const uint16_t *d_len,
+               uint32_t n, uint32_t off_unit_log2, const rxg_verdict *d_v, const rxg_l2_params *p,
+               uint8_t *d_status, uint8_t *d_out, uint64_t cap_bytes, uint32_t *d_roff,
+               uint16_t *d_rlen, uint32_t *d_rsrc, uint32_t *d_totals, void *stream) {
+    if (!c || !p || !d_totals || p->nlocal > RXG_L2_MAX_LOCAL) return RXG_EINVAL;
+    if (!d_status || !d_out || !d_roff || !d_rlen || !d_rsrc) return RXG_EINVAL;
+    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
+    if (n && (!d_pkts || !d_off || !d_len || !d_v)) return RXG_EINVAL;
+    if (((uintptr_t)d_out & 63u) || ((uintptr_t)d_roff & 3u) || ((uintptr_t)d_rsrc & 3u) ||
+        ((uintptr_t)d_rlen & 1u))
+        return RXG_EINVAL;
+    if (off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
+    DEVGUARD(c);
+    return l2_impl(c, d_pkts, d_off, d_len, n, off_unit_log2, reinterpret_cast<const uint4 *>(d_v), p,
+                   d_status, d_out, cap_bytes, d_roff, d_rlen, d_rsrc, d_totals, (hipStream_t)stream);
+}
+
+// the parameters are read at the next submit (by value into the launches); the
+// answer buffers follow cap_bytes there
+int rxg_l2_set(rxg_ctx *c, const rxg_l2_params *p, uint64_t cap_bytes) {
+    if (!c || !p || p->nlocal > RXG_L2_MAX_LOCAL) return RXG_EINVAL;
+    const uint64_t bound = c->max_bytes + 64ull * c->max_pkts;
+    c->l2_p = *p;
+    c->l2_cap = (cap_bytes < bound ? cap_bytes : bound) & ~63ull;
+    return RXG_OK;
+}
+
+int rxg_delivery_l2(rxg_ctx *c, const rxg_delivery *d, const uint8_t **status, const uint8_t **frames,
+                    const uint32_t **roff, const uint16_t **rlen, const uint32_t **rsrc, uint32_t *nans,
+                    uint32_t totals[6]) {
+    if (!c || !d || !status || !frames || !roff || !rlen || !rsrc || !nans || !totals) return RXG_EINVAL;
+    *status = nullptr, *frames = nullptr, *roff = nullptr, *rlen = nullptr, *rsrc = nullptr, *nans = 0;
+    memset(totals, 0, 6 * sizeof(uint32_t));
+    if (d->set < 1 || d->set > RXG_DELIVER_DEPTH) return RXG_EINVAL;
+    const rxg_ctx::delivery_set &ds = c->dls[d->set - 1];
+    if (ds.on) return RXG_EINVAL; // (not waited for yet)
+    if (!ds.l2) return RXG_OK;
+    *status = ds.h_l2_status, *frames = ds.h_l2_out;
+    *roff = ds.h_l2_roff, *rlen = ds.h_l2_rlen, *rsrc = ds.h_l2_rsrc;
+    *nans = ds.h_l2_totals[4];
+    memcpy(totals, ds.h_l2_totals, 6 * sizeof(uint32_t));
+    return RXG_OK;
+}
+
 int rxg_delivery_moved(rxg_ctx *c, const rxg_delivery *d, uint32_t *moved) {
     if (!c || !d || !moved) return RXG_EINVAL;
     *moved = 0;
@@ -2211,6 +2305,36 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
             HIPCHK(hipHostMalloc((void **)&ds.h_ck_txd, (size_t)c->max_pkts * sizeof(rxg_txd), 0));
         if (!ds.h_ck_totals) HIPCHK(hipHostMalloc((void **)&ds.h_ck_totals, 4 * sizeof(uint32_t), 0));
     }
+    const bool l2 = (c->deliver_flags & RXG_DLV_L2) != 0;
+    const uint64_t l2_room = c->l2_cap ? c->l2_cap : 64u; // (never a null answer buffer)
+    if (l2) {
+        if (!c->d_l2_status) HIPCHK(hipMalloc(&c->d_l2_status, c->max_pkts));
+        if (!c->d_l2_roff) HIPCHK(hipMalloc(&c->d_l2_roff, (size_t)c->max_pkts * sizeof(uint32_t)));
+        if (!c->d_l2_rlen) HIPCHK(hipMalloc(&c->d_l2_rlen, (size_t)c->max_pkts * sizeof(uint16_t)));
+        if (!c->d_l2_rsrc) HIPCHK(hipMalloc(&c->d_l2_rsrc, (size_t)c->max_pkts * sizeof(uint32_t)));
+        if (!c->d_l2_totals) HIPCHK(hipMalloc(&c->d_l2_totals, 6 * sizeof(uint32_t)));
+        if (c->d_l2_out_cap < l2_room) { // (a larger rxg_l2_set: after the bursts that use the old one)
+            HIPCHK(hipStreamSynchronize(c->stream));
+            (void)hipFree(c->d_l2_out);
+            c->d_l2_out = nullptr, c->d_l2_out_cap = 0;
+            HIPCHK(hipMalloc(&c->d_l2_out, l2_room));
+            c->d_l2_out_cap = l2_room;
+        }
+        if (!ds.h_l2_status) HIPCHK(hipHostMalloc((void **)&ds.h_l2_status, c->max_pkts, 0));
+        if (!ds.h_l2_roff)
+            HIPCHK(hipHostMalloc((void **)&ds.h_l2_roff, (size_t)c->max_pkts * sizeof(uint32_t), 0));
+        if (!ds.h_l2_rlen)
+            HIPCHK(hipHostMalloc((void **)&ds.h_l2_rlen, (size_t)c->max_pkts * sizeof(uint16_t), 0));
+        if (!ds.h_l2_rsrc)
+            HIPCHK(hipHostMalloc((void **)&ds.h_l2_rsrc, (size_t)c->max_pkts * sizeof(uint32_t), 0));
+        if (!ds.h_l2_totals) HIPCHK(hipHostMalloc((void **)&ds.h_l2_totals, 6 * sizeof(uint32_t), 0));
+        if (ds.h_l2_out_cap < l2_room) { // (this set has been waited for: nothing writes into it)
+            if (ds.h_l2_out) (void)hipHostFree(ds.h_l2_out);
+            ds.h_l2_out = nullptr, ds.h_l2_out_cap = 0;
+            HIPCHK(hipHostMalloc((void **)&ds.h_l2_out, l2_room, 0));
+            ds.h_l2_out_cap = l2_room;
+        }
+    }
     for (hipEvent_t &e : ds.tev)
         if (!e) HIPCHK(hipEventCreate(&e));
     // the TCP payloads of this burst: a free pooled buffer (a hold the caller
@@ -2245,7 +2369,7 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
         d->udp_payload = ds.h_cp_payload;
         memset(ds.h_cp_first, 0, (nf + 1) * sizeof(uint32_t));
     }
-    ds.on = ds.udp = ds.tcp = ds.gro = ds.order = ds.ddos = ds.assemble = ds.cookie = false;
+    ds.on = ds.udp = ds.tcp = ds.gro = ds.order = ds.ddos = ds.assemble = ds.cookie = ds.l2 = false;
     ds.nrun = ds.moved = ds.nstream = 0;
     ds.ticket = 0;
     ds.t0 = t0;
@@ -2319,6 +2443,15 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
                                      c->d_ck_status, c->d_ck_txd, c->d_ck_totals, c->stream)))
                 return rc;
         }
+        // the L2 responder (RXG_DLV_L2): K8 reads the verdicts and the ARP /
+        // echo frames; its status bytes, totals and answers go back with the
+        // other results
+        if (l2) {
+            if ((rc = l2_impl(c, sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, sl.d_out, &c->l2_p,
+                              c->d_l2_status, c->d_l2_out, c->l2_cap, c->d_l2_roff, c->d_l2_rlen,
+                              c->d_l2_rsrc, c->d_l2_totals, c->stream)))
+                return rc;
+        }
         HIPCHK(hipEventRecord(ds.tev[3], c->stream)); // after K3 / K4
         // every result in one round trip: the counts with upper-bound copies of
         // the records (n of each) and payloads (the staged span bounds the sum of
@@ -2360,6 +2493,24 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
                 HIPCHK(hipMemcpyAsync(ds.h_ck_txd, c->d_ck_txd, (size_t)n * sizeof(rxg_txd),
                                       hipMemcpyDeviceToHost, c->stream));
         }
+        if (l2) {
+            HIPCHK(hipMemcpyAsync(ds.h_l2_totals, c->d_l2_totals, 6 * sizeof(uint32_t),
+                                  hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(ds.h_l2_status, c->d_l2_status, n, hipMemcpyDeviceToHost, c->stream));
+            if (c->l2_p.nlocal && c->l2_cap) { // (else no answer)
+                // upper bounds: n entries, and every answer's slot is at most
+                // its frame's length rounded up to 64 B
+                const uint64_t bound = ((uint64_t)st.span + 64ull * n + 63u) & ~63ull;
+                HIPCHK(hipMemcpyAsync(ds.h_l2_roff, c->d_l2_roff, (size_t)n * sizeof(uint32_t),
+                                      hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(hipMemcpyAsync(ds.h_l2_rlen, c->d_l2_rlen, (size_t)n * sizeof(uint16_t),
+                                      hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(hipMemcpyAsync(ds.h_l2_rsrc, c->d_l2_rsrc, (size_t)n * sizeof(uint32_t),
+                                      hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(hipMemcpyAsync(ds.h_l2_out, c->d_l2_out, bound < c->l2_cap ? bound : c->l2_cap,
+                                      hipMemcpyDeviceToHost, c->stream));
+            }
+        }
         HIPCHK(hipEventRecord(ds.tev[4], c->stream)); // after the results' copy out
         return RXG_OK;
     };
@@ -2377,6 +2528,7 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
     ds.assemble = tcp && assemble;
     ds.ddos = ddos;
     ds.cookie = cookie;
+    ds.l2 = l2;
     ds.ticket = t;
     ds.t1 = t1;
     return RXG_OK;

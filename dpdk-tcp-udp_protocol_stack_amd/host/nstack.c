@@ -514,11 +514,92 @@ static void ck_host_burst(rxg_mbuf *const *m, uint32_t n, const rxg_verdict *v) 
     ck_take(s_ck_htx, tot);
     g_ck_st = s_ck_hst;
 }
+/* The L2 responder (nstack_set_l2_respond; the rule: rxgpu.h, "L2 responder"):
+ * ARP requests for the local address and echo requests to it are answered.
+ * Each burst is judged once (K8 with RXG_DLV_L2 on the device paths,
+ * rxg_l2_host in nstack_deliver); a frame whose burst result cannot be used
+ * (verdicts of an older snapshot, the option switched on between a submit and
+ * its delivery) is judged alone, by the same host call.  The answers are
+ * complete frames: copies wait in a bounded queue for the front of the next
+ * nstack_tx_burst.  All of it under g_lock. */
+#define L2_Q_FRAMES 1024u            /* answers waiting for a TX burst ... */
+#define L2_Q_BYTES (2u << 20)        /* ... and their 64-B slots; past either an answer is dropped */
+#define L2_BURST_BYTES (256u << 10)  /* the device paths' answer room per burst (rxg_l2_set) */
+static int g_l2;
+static uint64_t g_l2_arp, g_l2_echo, g_l2_drop, g_l2_bad; /* stat 21-24 */
+static struct l2_ans {
+    uint8_t *b;
+    uint32_t len;
+} s_l2q[L2_Q_FRAMES];                /* a ring: [g_l2q_head, g_l2q_head + g_l2q_n) */
+static uint32_t g_l2q_head, g_l2q_n;
+static uint64_t g_l2q_bytes;
+static uint8_t *s_l2_one;            /* the answer of a frame judged alone */
+static uint32_t g_local_ip;          /* nstack_set_local */
+static uint8_t g_local_mac[6];
+
+static void l2_params_now(rxg_l2_params *p) {
+    memset(p, 0, sizeof(*p));
+    p->nlocal = g_local_ip ? 1u : 0u;
+    p->local[0].ip = g_local_ip;
+    memcpy(p->local[0].mac, g_local_mac, 6);
+}
+/* the local address and the per-burst room to the context (g_lock held) */
+static int l2_sync(void) {
+    if (!g_l2 || !g_ctx) return RXG_OK;
+    rxg_l2_params p;
+    l2_params_now(&p);
+    return rxg_l2_set(g_ctx, &p, L2_BURST_BYTES);
+}
+static void l2_push(const uint8_t *f, uint32_t len, uint8_t st) {
+    const uint64_t slot = ((uint64_t)len + 63u) & ~63ull;
+    uint8_t *b = g_l2q_n < L2_Q_FRAMES && g_l2q_bytes + slot <= L2_Q_BYTES ? malloc(len) : NULL;
+    if (!b) {
+        g_l2_drop++;
+        return;
+    }
+    memcpy(b, f, len);
+    struct l2_ans *a = &s_l2q[(g_l2q_head + g_l2q_n) % L2_Q_FRAMES];
+    a->b = b, a->len = len;
+    g_l2q_n++, g_l2q_bytes += slot;
+    st == RXG_L2_ARP_REQ ? g_l2_arp++ : g_l2_echo++;
+}
+static void l2_q_clear(void) {
+    for (; g_l2q_n; g_l2q_n--, g_l2q_head = (g_l2q_head + 1) % L2_Q_FRAMES) free(s_l2q[g_l2q_head].b);
+    g_l2q_head = 0, g_l2q_bytes = 0;
+}
+/* a judged burst's answers and totals taken over; an answered frame whose
+ * answer the burst had no room for counts as dropped */
+static void l2_take(const uint8_t *status, const uint8_t *frames, const uint32_t *roff,
+                    const uint16_t *rlen, const uint32_t *rsrc, uint32_t nans, const uint32_t tot[6]) {
+    for (uint32_t k = 0; k < nans; k++) l2_push(frames + ((uint64_t)roff[k] << 6), rlen[k], status[rsrc[k]]);
+    g_l2_drop += (uint64_t)tot[0] + tot[2] - nans;
+    g_l2_bad += tot[3];
+}
+/* the frames of a burst judged one by one, each alone, by rxg_l2_host (the
+ * host-verdict path, and a device burst whose result cannot be used) */
+static void l2_host_frames(rxg_mbuf *const *m, uint32_t n, const rxg_verdict *v) {
+    if (!s_l2_one && !(s_l2_one = malloc(65536u + 64u))) return;
+    rxg_l2_params p;
+    l2_params_now(&p);
+    for (uint32_t i = 0; i < n; i++) {
+        if (v[i].cls != RXG_CLS_ARP && v[i].cls != RXG_CLS_IPV4_OTHER) continue;
+        const uint32_t off = 0;
+        const uint16_t len = m[i]->data_len;
+        uint8_t st = 0;
+        uint32_t roff, rsrc = 0, tot[6];
+        uint16_t rlen;
+        if (rxg_l2_host((const uint8_t *)m[i]->buf_addr + m[i]->data_off, &off, &len, 1, 4, &v[i], &p,
+                        &st, s_l2_one, 65536u + 64u, &roff, &rlen, &rsrc, tot) != RXG_OK)
+            continue;
+        l2_take(&st, s_l2_one, &roff, &rlen, &rsrc, tot[4], tot);
+    }
+}
 /* the delivery flags the options ask for (g_lock held) */
 static uint32_t dlv_flags(void) {
     return (g_inplace ? RXG_DLV_TCP_IN_PLACE : g_gro ? RXG_DLV_TCP_GRO : 0u) |
            (g_order ? RXG_DLV_TCP_ORDER : 0u) | (g_ddos ? RXG_DLV_DDOS : 0u) |
-           (g_assemble ? RXG_DLV_TCP_ASSEMBLE : 0u) | (g_ck_mode ? RXG_DLV_SYNCOOKIE : 0u);
+           (g_assemble ? RXG_DLV_TCP_ASSEMBLE : 0u) | (g_ck_mode ? RXG_DLV_SYNCOOKIE : 0u) |
+           (g_l2 ? RXG_DLV_L2 : 0u);
 }
 static void (*g_mb_release)(rxg_mbuf *m, void *arg);
 static void *g_mb_arg;
@@ -777,8 +858,6 @@ struct arp_entry {
     struct arp_entry *prev, *next;
 };
 static struct arp_entry *g_arp; /* head-inserted (LL_ADD, common.c:195) */
-static uint32_t g_local_ip;
-static uint8_t g_local_mac[6];
 static const uint8_t k_default_arp_mac[6] = {0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF}; /* netfamily.c:20 */
 static int g_burst_mutated;     /* the tcb list changed during this burst's delivery */
 static int g_rx_in_flight;      /* nstack_rx_burst waits for the GPU (g_lock released) */
@@ -1110,6 +1189,10 @@ int nstack_init(int device, uint32_t max_burst, uint64_t max_bytes) {
             rxg_tune_deliver(g_ctx, dlv_flags());
             (void)ck_sync_listeners();
         }
+        if (rc == RXG_OK && g_l2) {
+            rxg_tune_deliver(g_ctx, dlv_flags());
+            (void)l2_sync();
+        }
         /* a new context: its delivery sets start again at set 0 */
         for (uint32_t j = 0; j < RXG_DELIVER_DEPTH; j++) g_set_ref[j] = -1;
         g_next_set = 0;
@@ -1195,6 +1278,11 @@ void nstack_fini(void) {
     s_ck_hoff = NULL, s_ck_hlen = NULL;
     s_ck_mask_cap = g_ck_space = s_ck_tx_cap = g_ck_tx_head = g_ck_tx_n = s_ck_hcap = 0;
     g_ck_on = 0, g_ck_st = NULL;
+    g_l2 = 0;
+    g_l2_arp = g_l2_echo = g_l2_drop = g_l2_bad = 0;
+    l2_q_clear();
+    free(s_l2_one);
+    s_l2_one = NULL;
     g_tx_encode = 0;
     atomic_store_explicit(&g_txe_frames, 0, memory_order_relaxed);
     g_tx_mss = 0;
@@ -2121,6 +2209,7 @@ int nstack_deliver(rxg_mbuf *const *m, uint32_t n, const rxg_verdict *v, uint64_
             if (!g_burst_stale && n) ck_host_burst(m, n, v);
         }
         if (g_ddos && n) ddos_host_burst(m, n); /* (sees the frames; changes nothing below) */
+        if (g_l2 && n) l2_host_frames(m, n, v);  /* (the rule reads cls alone: stale or not) */
         const uint8_t *done = NULL;
         rxg_dgram *dg = NULL;
         uint32_t *first = NULL;
@@ -2841,6 +2930,19 @@ static int deliver_part(rxg_mbuf *const *m, uint32_t k, const rxg_verdict *v, ui
             ck_take(ctxd, ctot);
         else
             g_ck_st = NULL;
+    }
+    /* the L2 responder: the burst's answers when K8 ran at the submit, else the
+     * frames one by one */
+    if (g_l2) {
+        const uint8_t *lst = NULL, *lfr = NULL;
+        const uint32_t *lro = NULL, *lrs = NULL;
+        const uint16_t *lrl = NULL;
+        uint32_t lna = 0, ltot[6];
+        if (!g_burst_stale && rxg_delivery_l2(g_ctx, d, &lst, &lfr, &lro, &lrl, &lrs, &lna, ltot) == RXG_OK &&
+            lst)
+            l2_take(lst, lfr, lro, lrl, lrs, lna, ltot);
+        else
+            l2_host_frames(m, k, v);
     }
     rxg_ddos_summary dsum; /* (the detector on at the submit: the burst's summary) */
     if (g_ddos && rxg_delivery_ddos(g_ctx, d, &dsum) == RXG_OK) ddos_account(&dsum);
@@ -3674,8 +3776,21 @@ int nstack_set_local(uint32_t ip, const uint8_t mac[6]) {
     pthread_mutex_lock(&g_lock);
     g_local_ip = ip;
     if (mac) memcpy(g_local_mac, mac, 6);
+    (void)l2_sync(); /* (the responder answers for the address of its next burst) */
     pthread_mutex_unlock(&g_lock);
     return 0;
+}
+
+int nstack_set_l2_respond(int on) {
+    pthread_mutex_lock(&g_lock);
+    int rc = on && !g_local_ip ? RXG_EINVAL : RXG_OK;
+    if (rc == RXG_OK) {
+        g_l2 = on != 0;
+        if (g_ctx) rc = rxg_tune_deliver(g_ctx, dlv_flags());
+        if (rc == RXG_OK) rc = l2_sync();
+    }
+    pthread_mutex_unlock(&g_lock);
+    return rc;
 }
 
 int nstack_arp_insert(uint32_t ip, const uint8_t mac[6]) {
@@ -3816,6 +3931,25 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
             s_txseg = t, s_txseg_cap = max_frames;
         }
     }
+    /* the L2 responder's answers first, oldest first: complete frames, copied
+     * as they are; the walks below (and the encoder) get the room and the
+     * frame slots behind them */
+    while (g_l2q_n && n < max_frames && !full) {
+        struct l2_ans *a = &s_l2q[g_l2q_head];
+        if (pos + align64(a->len) > cap_bytes) {
+            full = 1;
+            break;
+        }
+        uint8_t *fp = pkts + pos;
+        memcpy(fp, a->b, a->len);
+        tx_place(fp, a->len, &pos, off, len, &n);
+        g_l2q_bytes -= align64(a->len);
+        free(a->b);
+        a->b = NULL;
+        g_l2q_head = (g_l2q_head + 1) % L2_Q_FRAMES, g_l2q_n--;
+    }
+    const uint32_t n0 = n;
+    const uint64_t pos0 = pos;
     /* udp_out, udp.c:123-164: at most one datagram per socket, list order */
     for (struct localhost *h = g_pstHost; h && n < max_frames && !full; h = h->next) {
         struct offload *o = NULL;
@@ -3990,21 +4124,24 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
     rxg_ctx *ctx = g_ctx;
     pthread_mutex_unlock(&g_lock);
     if (span) *span = pos;
-    if (cksum && n) {
+    if (cksum && n > n0) { /* (the responder's answers, frames [0, n0), are complete) */
         if (!ctx) return RXG_EINVAL;
         int rc;
+        const uint32_t nw = n - n0;
         if (enc) { /* K5 on the GPU: the frames, off and len of the walks' descriptors */
             uint64_t used = 0;
-            if (mss) /* n entries from nd descriptors */
-                rc = rxg_tx_encode_tso(ctx, s_txd, nd, s_txpay, s_txpay_len, mss, pkts, cap_bytes, off,
-                                       len, n, s_txseg, s_txseg + max_frames, 0, &used);
+            if (mss) /* nw entries from nd descriptors */
+                rc = rxg_tx_encode_tso(ctx, s_txd, nd, s_txpay, s_txpay_len, mss, pkts + pos0,
+                                       cap_bytes - pos0, off + n0, len + n0, nw, s_txseg,
+                                       s_txseg + max_frames, 0, &used);
             else
-                rc = rxg_tx_encode(ctx, s_txd, n, s_txpay, s_txpay_len, pkts, cap_bytes, off, len, 0,
-                                   &used);
-            if (rc == RXG_OK && used != pos) rc = RXG_ERANGE;
-            if (rc == RXG_OK) atomic_fetch_add_explicit(&g_txe_frames, n, memory_order_relaxed);
+                rc = rxg_tx_encode(ctx, s_txd, nw, s_txpay, s_txpay_len, pkts + pos0, cap_bytes - pos0,
+                                   off + n0, len + n0, 0, &used);
+            for (uint32_t k = n0; pos0 && k < n; k++) off[k] += (uint32_t)(pos0 >> 6);
+            if (rc == RXG_OK && used != pos - pos0) rc = RXG_ERANGE;
+            if (rc == RXG_OK) atomic_fetch_add_explicit(&g_txe_frames, nw, memory_order_relaxed);
         } else {
-            rc = rxg_tx_cksum(ctx, pkts, pos, off, len, n, 6); /* K2 on the GPU */
+            rc = rxg_tx_cksum(ctx, pkts, pos, off + n0, len + n0, nw, 6); /* K2 on the GPU */
         }
         if (rc) return rc;
     }
@@ -4012,7 +4149,14 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
 }
 
 uint64_t nstack_stat(int which) {
-    if (which < 0 || which > 20) return 0;
+    if (which < 0 || which > 24) return 0;
+    if (which >= 21) { /* the L2 responder: ARP / echo answers queued, answers dropped for
+                          room, echo requests with a bad checksum or a cut capture */
+        pthread_mutex_lock(&g_lock);
+        const uint64_t a = which == 21 ? g_l2_arp : which == 22 ? g_l2_echo : which == 23 ? g_l2_drop : g_l2_bad;
+        pthread_mutex_unlock(&g_lock);
+        return a;
+    }
     if (which >= 15) { /* segments absorbed by receive coalescing / moved by ordering; the
                           flood detector's frames under alarm / rises; stream assembly's
                           bytes already received / streams behind a hole */

@@ -243,6 +243,20 @@ _syncookie_set = _sig("rxg_syncookie_set", _i32, _vp, _vp, _vp, _u32)
 _syncookie_tick = _sig("rxg_syncookie_tick", _i32, _vp, _u32)
 _delivery_cookies = _sig("rxg_delivery_cookies", _i32, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp),
                          C.POINTER(_u32), _vp)
+# the L2 responder (K8): rxg_l2_params, the per-frame status values, the flag
+L2_MAX_LOCAL = 8
+L2_PARAMS_DTYPE = np.dtype([("nlocal", "<u4"),
+                            ("local", [("ip", "<u4"), ("mac", "u1", 6), ("_r", "<u2")], L2_MAX_LOCAL)])
+assert L2_PARAMS_DTYPE.itemsize == 100
+L2_ARP_REQ, L2_ARP_REPLY, L2_ECHO, L2_ECHO_BAD = 1, 2, 3, 4
+DLV_L2 = 0x100
+_l2_dev = _sig("rxg_l2_dev", _i32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u64, _vp, _vp,
+               _vp, _vp, _vp)
+_l2_host = _sig("rxg_l2_host", _i32, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp,
+                _vp)
+_l2_set = _sig("rxg_l2_set", _i32, _vp, _vp, _u64)
+_delivery_l2 = _sig("rxg_delivery_l2", _i32, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
+                    C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u32), _vp)
 _tune_deliver = _sig("rxg_tune_deliver", _i32, _vp, _u32)
 _tune_gro = _sig("rxg_tune_gro", _i32, _vp, _u32)
 _delivery_runs = _sig("rxg_delivery_runs", _i32, _vp, _vp, C.POINTER(_vp), C.POINTER(_u32))
@@ -349,7 +363,8 @@ EXPORTED = ["rxg_open", "rxg_close", "rxg_strerror", "rxg_last_hip_error", "rxg_
             "rxg_ddos_dev", "rxg_ddos_bits_dev", "rxg_ddos_window_dev", "rxg_ddos_host",
             "rxg_ddos_entropy", "rxg_tune_ddos", "rxg_tune_ddos_thresh", "rxg_ddos_reset",
             "rxg_delivery_ddos", "rxg_syncookie_value", "rxg_siphash24", "rxg_syncookie_dev",
-            "rxg_syncookie_host", "rxg_syncookie_set", "rxg_syncookie_tick", "rxg_delivery_cookies"]
+            "rxg_syncookie_host", "rxg_syncookie_set", "rxg_syncookie_tick", "rxg_delivery_cookies",
+            "rxg_l2_dev", "rxg_l2_host", "rxg_l2_set", "rxg_delivery_l2"]
 
 
 class RxgError(RuntimeError):
@@ -723,10 +738,50 @@ class Context:
                             np.uint8).copy().view(TXD_DTYPE) if nt.value else np.zeros(0, TXD_DTYPE)
         return status, txd, tot
 
+    def l2_dev(self, d_pkts, d_off, d_len, n: int, off_unit_log2: int, d_v, params: np.ndarray,
+               d_status, d_out, cap_bytes: int, d_roff, d_rlen, d_rsrc, d_totals, stream=None):
+        """rxg_l2_dev: one burst through the L2 responder (K8), async on
+        stream.  params: l2_params(); d_status (u8, n), d_out (u8, cap_bytes,
+        64-B aligned), d_roff / d_rsrc (u32, n), d_rlen (u16, n) and d_totals
+        (u32, 6) are device buffers"""
+        def p(x):
+            return x if (x is None or isinstance(x, int)) else x.data_ptr()
+        _check(_l2_dev(self._h, p(d_pkts), p(d_off), p(d_len), n, off_unit_log2, p(d_v), _ptr(params),
+                       p(d_status), p(d_out), cap_bytes, p(d_roff), p(d_rlen), p(d_rsrc), p(d_totals),
+                       stream), "rxg_l2_dev")
+
+    def l2_set(self, params: np.ndarray, cap_bytes: int):
+        """rxg_l2_set: the parameters (l2_params()) and the answers' room per
+        burst of the delivery bursts (DLV_L2)"""
+        _check(_l2_set(self._h, _ptr(params), cap_bytes), "rxg_l2_set")
+
+    def delivery_l2(self, handle=None):
+        """rxg_delivery_l2 of a waited-for deliver_submit handle (needs the
+        burst's n: handle), or of the last process_mbufs_deliver: copies of
+        (status u8[n], frames u8[64 * totals[5]], roff u32[k], rlen u16[k],
+        rsrc u32[k], totals u32[6]), k = totals[4]; (None, None, None, None,
+        None, zeros) with DLV_L2 off"""
+        d = handle[2] if handle is not None else self._last_delivery
+        n = len(handle[1]) if handle is not None else self._last_n
+        st, fr, ro, rl, rs, na = _vp(), _vp(), _vp(), _vp(), _vp(), _u32()
+        tot = np.zeros(6, np.uint32)
+        _check(_delivery_l2(self._h, C.byref(d), C.byref(st), C.byref(fr), C.byref(ro), C.byref(rl),
+                            C.byref(rs), C.byref(na), _ptr(tot)), "rxg_delivery_l2")
+        if not st.value:
+            return None, None, None, None, None, tot
+
+        def take(ptr, nbytes, dt):
+            if not nbytes:
+                return np.zeros(0, dt)
+            return np.frombuffer((C.c_uint8 * nbytes).from_address(ptr.value), np.uint8).copy().view(dt)
+        k = na.value
+        return (take(st, n, np.uint8), take(fr, 64 * int(tot[5]), np.uint8), take(ro, 4 * k, np.uint32),
+                take(rl, 2 * k, np.uint16), take(rs, 4 * k, np.uint32), tot)
+
     def tune_deliver(self, flags: int):
         """rxg_tune_deliver: DLV_TCP_IN_PLACE or DLV_TCP_GRO, either with
         DLV_TCP_ORDER; or DLV_TCP_ASSEMBLE (with or without DLV_TCP_ORDER); any
-        of them with DLV_DDOS and DLV_SYNCOOKIE (0 = the default)"""
+        of them with DLV_DDOS, DLV_SYNCOOKIE and DLV_L2 (0 = the default)"""
         _check(_tune_deliver(self._h, flags), "rxg_tune_deliver")
 
     def tune_gro(self, window: int):
@@ -1016,6 +1071,44 @@ def ck_params(key: bytes, t: int, max_age: int = CK_DEFAULT_MAX_AGE, window: int
     p["k0"], p["k1"] = int.from_bytes(key[:8], "little"), int.from_bytes(key[8:], "little")
     p["t"], p["max_age"], p["window"] = t & 0xFFFFFFFF, max_age, window
     return p
+
+
+def l2_params(local) -> np.ndarray:
+    """rxg_l2_params (one element) from (ip, mac) pairs: ip dotted or raw,
+    mac six bytes"""
+    p = np.zeros(1, L2_PARAMS_DTYPE)
+    p["nlocal"] = len(local)
+    for j, (ip, mac) in enumerate(local[:L2_MAX_LOCAL]):
+        p["local"][0, j]["ip"] = ip_raw(ip) if isinstance(ip, str) else ip
+        p["local"][0, j]["mac"] = np.frombuffer(bytes(mac), np.uint8)
+    return p
+
+
+def l2_host(pkts: np.ndarray, off: np.ndarray, lens: np.ndarray, off_unit_log2: int,
+            verdicts: np.ndarray, params: np.ndarray, cap_bytes: int, pad: int = 0, canary: int = 0):
+    """rxg_l2_host: one burst through the L2 responder on the CPU: (status,
+    frames, roff, rlen, rsrc, totals), the arrays cut to what was written.  With
+    pad, they are returned whole: n + pad entries each and cap_bytes + 64 * pad
+    bytes of frames, pre-filled with canary"""
+    n = len(lens)
+    pkts = np.ascontiguousarray(pkts, np.uint8)
+    off = np.ascontiguousarray(off, np.uint32)
+    lens = np.ascontiguousarray(lens, np.uint16)
+    v = np.ascontiguousarray(verdicts, VERDICT_DTYPE)
+    status = np.full(n + pad, canary, np.uint8)
+    out = np.full(cap_bytes + 64 * pad + 64, canary, np.uint8)
+    out = out[(-out.ctypes.data) % 64:][:cap_bytes + 64 * pad]
+    roff = np.full(n + pad, canary * 0x01010101, np.uint32)
+    rlen = np.full(n + pad, canary * 0x0101, np.uint16)
+    rsrc = np.full(n + pad, canary * 0x01010101, np.uint32)
+    tot = np.zeros(6, np.uint32)
+    _check(_l2_host(pkts.ctypes.data if n else None, off.ctypes.data, lens.ctypes.data, n, off_unit_log2,
+                    v.ctypes.data, _ptr(params), status.ctypes.data, out.ctypes.data, cap_bytes,
+                    roff.ctypes.data, rlen.ctypes.data, rsrc.ctypes.data, tot.ctypes.data), "rxg_l2_host")
+    if pad:
+        return status, out, roff, rlen, rsrc, tot
+    k = int(tot[4])
+    return status, out[:64 * int(tot[5])].copy(), roff[:k].copy(), rlen[:k].copy(), rsrc[:k].copy(), tot
 
 
 def siphash24(key: bytes, msg: bytes) -> int:
@@ -1313,7 +1406,8 @@ class NStack:
                    ("nstack_ddos_status", _i32, [_vp]),
                    ("nstack_set_syncookies", _i32, [_i32, _vp]),
                    ("nstack_syncookie_tick", _i32, [_u32]),
-                   ("nstack_syncookie_stats", _i32, [_vp])]
+                   ("nstack_syncookie_stats", _i32, [_vp]),
+                   ("nstack_set_l2_respond", _i32, [_i32])]
             for name, res, args in sig:
                 f = getattr(lib, name)
                 f.restype, f.argtypes = res, args
@@ -1664,6 +1758,14 @@ class NStack:
         out = np.zeros(4, np.uint64)
         _check(self.lib.nstack_syncookie_stats(out.ctypes.data), "nstack_syncookie_stats")
         return {"syn_answered": int(out[0]), "accepted": int(out[1]), "rejected": int(out[2])}
+
+    def set_l2_respond(self, on: bool = True):
+        """nstack_set_l2_respond: ARP requests for set_local's address and echo
+        requests to it are answered out of the next tx_burst (stat(21) ARP /
+        stat(22) echo answers queued, stat(23) dropped for room, stat(24) echo
+        requests with a bad checksum or a cut capture); raises RxgError
+        (RXG_EINVAL) while no local address is set"""
+        _check(self.lib.nstack_set_l2_respond(1 if on else 0), "nstack_set_l2_respond")
 
     def tx_burst(self, max_frames: int = 256, cap_bytes: int = 1 << 20, cksum: bool = False):
         """one udp_out + tcp_out pass: the frames (bytes) it produced"""

@@ -362,6 +362,28 @@ int nstack_ddos_status(nstack_ddos *out);
 int nstack_set_syncookies(int mode, const uint8_t key[16]);
 int nstack_syncookie_tick(uint32_t t);
 int nstack_syncookie_stats(uint64_t out[4]);
+/* The L2 responder (the rule: rxgpu.h, "L2 responder"; off by default): with
+ * it on, an ARP request for nstack_set_local's address and an ICMP echo request
+ * to it are answered by the stack itself (the reference leaves both to the
+ * kernel behind KNI, which this project does not forward to), so a peer can
+ * resolve the stack and ping it.  RXG_EINVAL while no local address is set.
+ * The device paths (nstack_rx_burst, the halves, nstack_rx_submit /
+ * nstack_rx_complete) run K8 with RXG_DLV_L2 and room for 256 KiB of answers
+ * per burst; the host-verdict path (nstack_deliver) runs rxg_l2_host; a frame
+ * whose burst result cannot be used (a burst whose lists changed under it,
+ * nstack_stat(5)) is judged alone by the same host call.  The answers are
+ * complete frames: copies wait in a queue of at most 1024 frames or 2 MiB of
+ * 64-B slots (past either an answer is dropped and counted) and leave at the
+ * front of the next nstack_tx_burst, ahead of the UDP and TCP walks, under its
+ * max_frames and cap_bytes (what does not fit stays queued), with cksum 0 or
+ * not and with nstack_set_tx_encode on or off: the encoder gets the room and
+ * the frame slots behind them.  ARP learning is what it is without the
+ * option.  Limits: one local address, no IPv4 options, no fragments, no rate
+ * limit beyond the per-burst room and the queue.  nstack_stat(21) counts the
+ * ARP answers queued, (22) the echo answers queued, (23) the answers dropped
+ * for room, (24) the echo requests with a bad checksum or a cut capture.
+ * nstack_fini resets the option, the queue and the counts. */
+int nstack_set_l2_respond(int on);
 /* Items the application has read (fragments, datagram batches) are handed
  * back to the protocol thread and freed by its next nstack_rx_burst (while
  * that burst is on the GPU) / nstack_tx_burst / nstack_deliver call (or
@@ -416,7 +438,9 @@ int nstack_set_halves(uint32_t min_half);
  * ordering (nstack_set_rx_order); 17 = frames received under the flood detector's
  * alarm, 18 = its rises (nstack_set_rx_ddos); 19 = payload bytes discarded as
  * already received, 20 = streams ignored behind a hole
- * (nstack_set_rx_assemble).  Counter 1 also counts TX items dropped (a
+ * (nstack_set_rx_assemble); 21-24 = the L2 responder's ARP answers queued,
+ * echo answers queued, answers dropped for room, echo requests with a bad
+ * checksum or a cut capture (nstack_set_l2_respond).  Counter 1 also counts TX items dropped (a
  * send ring full, or a datagram too long for a frame). */
 uint64_t nstack_stat(int which);
 

@@ -884,6 +884,98 @@ int rxg_syncookie_tick(rxg_ctx *ctx, uint32_t t);
 int rxg_delivery_cookies(rxg_ctx *ctx, const rxg_delivery *d, const uint8_t **status,
                          const struct rxg_txd **txd, uint32_t *ntxd, uint32_t totals[4]);
 
+/* ---- L2 responder (K8, csrc/rx_l2.hip; opt-in)
+ * ARP requests for a local address and ICMP echo requests to one are answered
+ * on the device: K1 keeps handing both to KNI (cls RXG_CLS_ARP /
+ * RXG_CLS_IPV4_OTHER, rc RXG_RC_KNI, on or off), and this pass, behind K1,
+ * writes the complete answer frames.  Addresses are raw network order; offsets
+ * are frame offsets; nothing past a frame's captured length is read (beyond
+ * the 16-B piece that holds its last byte); nlocal == 0 makes no frame a
+ * candidate.
+ * ARP: frame i is a candidate when its verdict has cls RXG_CLS_ARP,
+ *   len >= 42, bytes 14-19 are 00 01 08 00 06 04, the Ethernet source is not a
+ *   group address (byte 6 & 1 == 0) and the target protocol address (bytes
+ *   38-41) equals some local[j].ip (first match).  Opcode (BE bytes 20-21) 1:
+ *   RXG_L2_ARP_REQ, answered; 2: RXG_L2_ARP_REPLY, not answered (the frame is
+ *   addressed to us); any other: 0.  The answer (42 bytes, RFC 826 opcode 2):
+ *   dst = request bytes 22-27 (sha), src = local[j].mac, type 0806,
+ *   00 01 08 00 06 04 00 02, sha = local[j].mac, spa = the request's tpa,
+ *   tha = the request's sha, tpa = the request's spa.
+ * Echo: frame i is a candidate when its verdict has cls RXG_CLS_IPV4_OTHER,
+ *   len >= 42, byte 14 is 0x45 (a header with options is not answered: this
+ *   pass does not apply the "IHL ignored" convention), byte 23 is 1,
+ *   (BE16(20-21) & 0x3FFF) == 0 (no fragment), byte 6 & 1 == 0, bytes 30-33
+ *   equal some local[j].ip, byte 34 is 8, byte 35 is 0, and tl = BE16(16-17)
+ *   is >= 28.  M = bytes [34, 14 + tl).  If 14 + tl > len, or the
+ *   one's-complement sum of M (odd tail byte padded with zero, stored checksum
+ *   included) does not fold to 0xFFFF: RXG_L2_ECHO_BAD, nothing written.
+ *   Otherwise RXG_L2_ECHO, answered.  The answer (14 + tl bytes): dst = request
+ *   bytes 6-11, src = local[j].mac, type 0800; a fresh IPv4 header as the TX
+ *   encoders below write it (45 00, tl, id 0, fragment 0, ttl 64, proto 1,
+ *   header checksum the plain complement, sip = request dip, dip = request
+ *   sip); ICMP type 0, code 0, then request bytes [38, 14 + tl) unchanged; the
+ *   ICMP checksum at 36-37 is computed over the answer's message with its
+ *   field taken as 0, plain complement (a sum of 0xFFFF stores 0).
+ * Every other frame: status 0.
+ * Layout (K5's packed form): answers in burst order, answer k at the
+ * 64-B-rounded end of answer k-1 (the first at 0), each zero-filled to its
+ * next 64-B boundary; roff[k] in 64-B units, rlen[k] the answer's length,
+ * rsrc[k] the index of the frame it answers.  The first answer whose slot
+ * would pass cap_bytes ends the output: it and every later answer are not
+ * written (status bytes are unaffected).  totals = {ARP_REQ, ARP_REPLY, ECHO,
+ * ECHO_BAD frames, answers written, span in 64-B units}.  No byte of the
+ * output at or past the span, no roff / rlen / rsrc entry at or past "answers
+ * written" and no status byte at or past n is written.  The span of a burst
+ * must stay below 2^32 64-B units. */
+#define RXG_L2_MAX_LOCAL 8
+typedef struct rxg_l2_params {
+    uint32_t nlocal; /* <= RXG_L2_MAX_LOCAL */
+    struct {
+        uint32_t ip;    /* raw network order */
+        uint8_t mac[6];
+        uint16_t _r;
+    } local[RXG_L2_MAX_LOCAL];
+} rxg_l2_params; /* 100 bytes */
+#define RXG_L2_ARP_REQ 1
+#define RXG_L2_ARP_REPLY 2
+#define RXG_L2_ECHO 3
+#define RXG_L2_ECHO_BAD 4
+/* One burst on the device, asynchronous on `stream`.  Frames as for
+ * rxg_syncookie_dev (off_unit_log2 >= 4, 16-B aligned frame starts), d_v the
+ * burst's 16-B verdicts.  *p is read at call time.  d_status: n bytes (any
+ * alignment); d_out: cap_bytes of answer memory, 64-B aligned; d_roff /
+ * d_rlen / d_rsrc: room for n entries; d_totals: 6 words, always written.
+ * n == 0 zeroes the totals without a launch.  RXG_EINVAL for nlocal >
+ * RXG_L2_MAX_LOCAL and for NULL outputs.  Calls on one context share its
+ * workspace (grown on demand in stream order) and must be ordered by the
+ * caller. */
+int rxg_l2_dev(rxg_ctx *ctx, const uint8_t *d_pkts, const uint32_t *d_off, const uint16_t *d_len,
+               uint32_t n, uint32_t off_unit_log2, const rxg_verdict *d_v, const rxg_l2_params *p,
+               uint8_t *d_status, uint8_t *d_out, uint64_t cap_bytes, uint32_t *d_roff,
+               uint16_t *d_rlen, uint32_t *d_rsrc, uint32_t *d_totals, void *stream);
+/* The same on the CPU (csrc/rx_l2_host.cpp): no context, no device; the path
+ * of callers without a GPU and the tests' second opinion, never a fallback the
+ * device call takes. */
+int rxg_l2_host(const uint8_t *pkts, const uint32_t *off, const uint16_t *len, uint32_t n,
+                uint32_t off_unit_log2, const rxg_verdict *v, const rxg_l2_params *p, uint8_t *status,
+                uint8_t *out, uint64_t cap_bytes, uint32_t *roff, uint16_t *rlen, uint32_t *rsrc,
+                uint32_t totals[6]);
+/* RXG_DLV_L2 (rxg_tune_deliver, combinable with every other flag): a delivery
+ * burst also runs K8 on the context's stream behind K1, with the parameters
+ * and answer capacity of rxg_l2_set (cap_bytes is rounded down to 64 B and
+ * bounded by the context's max_bytes + 64 * max_pkts; without rxg_l2_set no
+ * frame is a candidate).  The n status bytes, the totals, an upper-bound copy
+ * of roff / rlen / rsrc and of the answers' bytes cross PCIe with the other
+ * results; verdicts, records and payloads are what they are without the flag.
+ * rxg_delivery_l2 returns them for a waited-for burst, valid as long as the
+ * burst's delivery set is; NULL / 0 when the flag was off for it.  struct
+ * rxg_delivery is unchanged.  Off by default. */
+#define RXG_DLV_L2 0x100u
+int rxg_l2_set(rxg_ctx *ctx, const rxg_l2_params *p, uint64_t cap_bytes);
+int rxg_delivery_l2(rxg_ctx *ctx, const rxg_delivery *d, const uint8_t **status,
+                    const uint8_t **frames, const uint32_t **roff, const uint16_t **rlen,
+                    const uint32_t **rsrc, uint32_t *nans, uint32_t totals[6]);
+
 /* TX checksum generation (the send side's per-frame work, udp.c:84-95 and
  * tcp.c:444-463): for every IPv4 frame of the burst, the IPv4 header checksum
  * (rte_ipv4_cksum, rte_ip.h:255-265) is written at frame offset 24, and for
