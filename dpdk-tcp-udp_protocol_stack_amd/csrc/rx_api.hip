@@ -1793,6 +1793,11 @@ int rxg_udp_compact_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off
     if (off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
     DEVGUARD(c);
     if (c->fs.udp.id_space() > RXG_COMPACT_MAX_FLOWS) return RXG_ERANGE;
+    if (c->fs.udp.id_space() == 0) { // no UDP ids: nothing is delivered (compact_impl writes nothing)
+        HIPCHK(hipMemsetAsync(d_totals, 0, 3 * sizeof(uint32_t), (hipStream_t)stream));
+        HIPCHK(hipMemsetAsync(d_first, 0, sizeof(uint32_t), (hipStream_t)stream));
+        return RXG_OK;
+    }
     return compact_impl(c, d_pkts, d_off, d_len, n, off_unit_log2,
                         reinterpret_cast<const uint4 *>(d_v), d_dgram, d_first, d_payload,
                         payload_cap, d_totals, (hipStream_t)stream);

@@ -334,7 +334,9 @@ typedef struct rxg_dgram {
  * datagrams of UDP id f get ranks [d_first[f], d_first[f+1]) of d_dgram (so
  * d_first has rxg_num_udp_ids() + 1 entries, d_dgram room for n); d_totals =
  * {datagrams, payload bytes used, 1 if payload_cap was too small (those
- * payloads are not written)}.  RXG_ERANGE above RXG_COMPACT_MAX_FLOWS ids. */
+ * payloads are not written)}.  With no UDP ids at all, d_totals[0..2] and
+ * d_first[0] are cleared to 0 on `stream` and nothing else is written.
+ * RXG_ERANGE above RXG_COMPACT_MAX_FLOWS ids (nothing is written). */
 int rxg_udp_compact_dev(rxg_ctx *ctx, const uint8_t *d_pkts, const uint32_t *d_off,
                         const uint16_t *d_len, uint32_t n, uint32_t off_unit_log2,
                         const rxg_verdict *d_v, rxg_dgram *d_dgram, uint32_t *d_first,

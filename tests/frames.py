@@ -112,6 +112,28 @@ def pack_frames(frames: list[bytes], unit_log2: int = 6, caplens=None):
     return buf, np.array(offs, np.uint32), np.array(lens, np.uint16)
 
 
+def pack_filled(frames: list[bytes], unit_log2: int = 4, caplens=None, fill: int = 0xEE,
+                mem_order=None, tail: int = 64):
+    """pack_frames with nothing but `fill` outside the frames' own bytes and,
+    with mem_order (a permutation), frame mem_order[k] the k-th in memory
+    while descriptor i still names frames[i]: slots back to back, each the
+    frame's bytes (the captured length if that is longer) rounded up to the
+    unit, so at unit_log2 = 4 a frame's neighbours start right after its
+    16-B end; `tail` fill bytes close the buffer"""
+    unit = 1 << unit_log2
+    n = len(frames)
+    lens = [len(f) for f in frames] if caplens is None else [int(c) for c in caplens]
+    offs, pos = [0] * n, 0
+    for i in (range(n) if mem_order is None else mem_order):
+        offs[int(i)] = pos // unit
+        pos += max(unit, (max(len(frames[int(i)]), lens[int(i)]) + unit - 1) // unit * unit)
+    buf = np.full(pos + tail, fill, np.uint8)
+    for i, f in enumerate(frames):
+        o = offs[i] * unit
+        buf[o:o + len(f)] = np.frombuffer(f, np.uint8)
+    return buf, np.array(offs, np.uint32), np.array(lens, np.uint16)
+
+
 # ---- classic pcap ---------------------------------------------------------
 def write_pcap(path: str, frames: list[bytes], caplens=None):
     with open(path, "wb") as fh:

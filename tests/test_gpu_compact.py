@@ -17,6 +17,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import compact_ref as CR
 import frames as F
 import gro_ref as G
 import oracle_bind as O
@@ -81,24 +82,13 @@ def test_compaction_matches_model(torch_dev):
         dg = d_dg.cpu().numpy().view(R.DGRAM_DTYPE)[:tot[0]]
         pl = d_pl.cpu().numpy()
     assert tot[2] == 0
-    deliv = np.nonzero((v["cls"] == R.CLS_UDP) & (v["rc"] == 0))[0]
-    order = deliv[np.argsort(v["flow_id"][deliv], kind="stable")]  # by socket, burst order inside
-    assert tot[0] == len(order) and np.array_equal(dg["frame"], order)
-    assert np.array_equal(first, np.searchsorted(v["flow_id"][order], np.arange(nsock + 1)))
-    pos = 0
-    for r, i in enumerate(order):
-        f = frames[i][:caps[i]]
-        plen = int(v["payload_len"][i])
-        ncopy = max(0, min(plen, len(f) - 42))
-        d = dg[r]
-        assert d["offset"] == pos and d["len"] == plen, r
-        assert d["sip"] == int.from_bytes((f + bytes(64))[26:30], "little")
-        assert d["sport"] == int.from_bytes((f + bytes(64))[34:36], "little")
-        assert pl[pos:pos + ncopy].tobytes() == f[42:42 + ncopy], r
-        pad = (ncopy + 15) // 16 * 16
-        assert not pl[pos + ncopy:pos + pad].any(), r
-        pos += pad
-    assert tot[1] == pos
+    want = CR.compact(frames, caps, v, nsock, cap)  # tests/compact_ref.py: by socket, burst order inside
+    assert list(tot) == list(want.totals) and tot[0] > 4000
+    assert np.array_equal(first, want.first)
+    bad = [r for r in range(len(dg)) if dg[r].tobytes() != want.dgram[r].tobytes()]
+    assert not bad, [(r, dg[r], want.dgram[r]) for r in bad[:5]]
+    assert pl[:tot[1]].tobytes() == want.payload.tobytes()  # every payload byte and the zero padding
+    assert np.all(pl[tot[1]:] == 0xCD)
 
 
 def test_socket_layer_batches_match_oracle(torch_dev):
