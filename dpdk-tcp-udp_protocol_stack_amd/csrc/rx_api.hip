@@ -214,6 +214,28 @@ struct rx_track {
 };
 #define RX_TRACK 4
 
+// The form of K4 (rx_segsort.hip) a call or a delivery burst runs, derived once
+// from the RXG_DLV_* flags: it gives the workspace size and the number of
+// totals words (tcp_launch below runs it).
+struct k4_form {
+    bool gro = false, order = false, assemble = false;
+    bool inplace = false; // records only: no payload is gathered
+    static k4_form of(uint32_t dlv) {
+        k4_form f;
+        f.gro = (dlv & RXG_DLV_TCP_GRO) != 0;
+        f.assemble = (dlv & RXG_DLV_TCP_ASSEMBLE) != 0;
+        // (assembly runs the ordering stage itself and reports its moved count)
+        f.order = (dlv & RXG_DLV_TCP_ORDER) != 0 || f.assemble;
+        f.inplace = (dlv & RXG_DLV_TCP_IN_PLACE) != 0;
+        return f;
+    }
+    uint32_t ntotals() const { return assemble ? 6u : order ? 5u : gro ? 4u : 3u; }
+    size_t ws_bytes(uint32_t n) const {
+        return assemble ? rx_assemble_ws_bytes(n) : order ? rx_order_ws_bytes(n)
+               : gro    ? rx_gro_ws_bytes(n) : rx_segsort_ws_bytes(n);
+    }
+};
+
 struct rxg_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -235,42 +257,60 @@ struct rxg_ctx {
     uint32_t tune_tables = 0; // rxg_tune_tables flags
     uint32_t tune_ingest = RXG_INGEST_AUTO; // rxg_tune_ingest
     uint32_t deliver_flags = 0;             // rxg_tune_deliver (RXG_DLV_*)
-    uint32_t gro_window = RXG_GRO_DEFAULT_WINDOW; // rxg_tune_gro (RXG_DLV_TCP_GRO)
-    // the entropy flood detector (K6, rx_ddos.hip): rxg_tune_ddos /
-    // rxg_tune_ddos_thresh, the workspace of every detector call on this
-    // context, and the state and summary of the delivery bursts (RXG_DLV_DDOS)
-    uint32_t tune_ddos = 0;
-    double ddos_thresh = RXG_DDOS_DEFAULT_THRESH;
-    void *d_ddos_ws = nullptr;
-    size_t d_ddos_ws_cap = 0;
-    rxg_ddos_state *d_ddos_state = nullptr;
-    rxg_ddos_summary *d_ddos_sum = nullptr;
-    // SYN cookies (K7, rx_syncookie.hip): the workspace of every call on this
-    // context; for the delivery bursts (RXG_DLV_SYNCOOKIE) the parameters and
-    // listener mask of rxg_syncookie_set (ck_hmask: the upload's source, kept
-    // until ev_ck says it has been read) and the device results
-    void *d_ck_ws = nullptr;
-    size_t d_ck_ws_cap = 0;
-    rxg_ck_params ck_p{};
-    uint32_t ck_id_space = 0;
-    std::vector<uint32_t> ck_hmask;
-    void *d_ck_mask = nullptr;
-    size_t d_ck_mask_cap = 0;
-    hipEvent_t ev_ck = nullptr;
-    uint8_t *d_ck_status = nullptr;
-    rxg_txd *d_ck_txd = nullptr;
-    uint32_t *d_ck_totals = nullptr;
-    // the L2 responder (K8, rx_l2.hip): the workspace of every call on this
-    // context; for the delivery bursts (RXG_DLV_L2) the parameters and answer
-    // capacity of rxg_l2_set and the device results
-    void *d_l2_ws = nullptr;
-    size_t d_l2_ws_cap = 0;
-    rxg_l2_params l2_p{};
-    uint64_t l2_cap = 0;
-    uint8_t *d_l2_status = nullptr, *d_l2_out = nullptr;
-    uint64_t d_l2_out_cap = 0;
-    uint32_t *d_l2_roff = nullptr, *d_l2_rsrc = nullptr, *d_l2_totals = nullptr;
-    uint16_t *d_l2_rlen = nullptr;
+    // The burst passes behind the classify, one struct each: what its
+    // rxg_tune_* / rxg_*_set call left, its workspace (ws_grow; every call on
+    // this context shares it) and the device results of the delivery bursts
+    // (first use: rxg_deliver_submit).  The pinned copies: delivery_set below.
+    struct ws_buf { void *p = nullptr; size_t cap = 0; };
+    struct udp_host { // one group of pinned copies of K3's results
+        rxg_dgram *h_dg = nullptr;
+        uint32_t *h_first = nullptr, *h_totals = nullptr;
+        uint8_t *h_payload = nullptr;
+    };
+    struct udp_pass { // UDP compaction (K3, rx_compact.hip); sized by max_pkts / max_bytes
+        rxg_dgram *d_dg = nullptr;
+        uint32_t *d_first = nullptr, *d_totals = nullptr;
+        uint8_t *d_payload = nullptr;
+        ws_buf ws;
+        udp_host own; // rxg_process_mbufs_udp's copies (it uses no delivery set)
+    } udp;
+    struct tcp_pass { // TCP segment sort + payload gather (K4 and its forms, rx_segsort.hip)
+        uint32_t window = RXG_GRO_DEFAULT_WINDOW; // rxg_tune_gro (RXG_DLV_TCP_GRO)
+        rxg_segment *d_seg = nullptr;
+        uint8_t *d_payload = nullptr;
+        rxg_tcp_run *d_run = nullptr;       // (RXG_DLV_TCP_GRO: first use)
+        rxg_tcp_stream *d_stream = nullptr; // (RXG_DLV_TCP_ASSEMBLE: first use)
+        uint32_t *d_totals = nullptr;
+        ws_buf ws; // one buffer for all four forms
+    } tcp;
+    struct ddos_pass { // the entropy flood detector (K6, rx_ddos.hip)
+        uint32_t lanes = 0;                       // rxg_tune_ddos
+        double thresh = RXG_DDOS_DEFAULT_THRESH;  // rxg_tune_ddos_thresh
+        ws_buf ws;
+        rxg_ddos_state *d_state = nullptr; // the state the delivery bursts carry (RXG_DLV_DDOS)
+        rxg_ddos_summary *d_sum = nullptr;
+    } ddos;
+    struct cookie_pass { // SYN cookies (K7, rx_syncookie.hip)
+        ws_buf ws;
+        rxg_ck_params p{}; // rxg_syncookie_set, with the listener mask (hmask: the upload's source,
+                           // kept until ev says it has been read)
+        uint32_t id_space = 0;
+        std::vector<uint32_t> hmask;
+        ws_buf mask;
+        hipEvent_t ev = nullptr;
+        uint8_t *d_status = nullptr;
+        rxg_txd *d_txd = nullptr;
+        uint32_t *d_totals = nullptr;
+    } ck;
+    struct l2_pass { // the L2 responder (K8, rx_l2.hip)
+        ws_buf ws;
+        rxg_l2_params p{}; // rxg_l2_set, with the answer capacity
+        uint64_t cap = 0;
+        uint8_t *d_status = nullptr, *d_out = nullptr;
+        uint64_t d_out_cap = 0;
+        uint32_t *d_roff = nullptr, *d_rsrc = nullptr, *d_totals = nullptr;
+        uint16_t *d_rlen = nullptr;
+    } l2;
     rx_ft_dev ft{};
     uint32_t tune_g = 0, tune_p = 0, tune_fpg = 0, tune_pipe = ~0u; // rxg_tune override
     uint32_t tune_bpc = 0; // rxg_tune_grid: resident blocks per CU cap (0 = occupancy)
@@ -337,20 +377,6 @@ struct rxg_ctx {
         uint64_t ticket = 0;          // last burst submitted to this slot (0 = none)
     } slots[RXG_PIPE_DEPTH];
     uint64_t next_ticket = 1;
-    // UDP compaction results of the host-buffer path (rxg_process_mbufs_udp):
-    // device buffers and their pinned host copies, sized by max_pkts / max_bytes
-    rxg_dgram *d_cp_dg = nullptr, *h_cp_dg = nullptr;
-    uint32_t *d_cp_first = nullptr, *h_cp_first = nullptr;
-    uint8_t *d_cp_payload = nullptr, *h_cp_payload = nullptr;
-    uint32_t *d_cp_totals = nullptr, *h_cp_totals = nullptr;
-    void *d_cp_ws = nullptr;
-    size_t d_cp_ws_cap = 0;
-    // TCP segment sort + payload gather (K4, rxg_process_mbufs_deliver): device
-    // results and their pinned host copies, sized by max_pkts / max_bytes
-    rxg_segment *d_ss_seg = nullptr;
-    uint8_t *d_ss_payload = nullptr;
-    rxg_tcp_run *d_ss_run = nullptr; // (RXG_DLV_TCP_GRO: first use)
-    rxg_tcp_stream *d_ss_stream = nullptr; // (RXG_DLV_TCP_ASSEMBLE: first use)
     // pinned payload buffers a caller may keep past the next burst
     // (rxg_payload_hold / _release: the receive fragments of a burst point
     // into them until the application has read them); refs counts the holds,
@@ -364,38 +390,40 @@ struct rxg_ctx {
     // device buffers are shared: every step runs on `stream`, in order) and its
     // phase events; a set's results stay valid until the set is reused
     struct delivery_set {
-        bool on = false, udp = false, tcp = false, gro = false, order = false, ddos = false;
-        bool assemble = false;
-        bool l2 = false;               // (rxg_delivery_l2)
-        uint8_t *h_l2_status = nullptr, *h_l2_out = nullptr;
-        uint64_t h_l2_out_cap = 0;
-        uint32_t *h_l2_roff = nullptr, *h_l2_rsrc = nullptr, *h_l2_totals = nullptr;
-        uint16_t *h_l2_rlen = nullptr;
-        bool cookie = false;           // (rxg_delivery_cookies)
-        uint8_t *h_ck_status = nullptr;
-        rxg_txd *h_ck_txd = nullptr;
-        uint32_t *h_ck_totals = nullptr;
-        uint32_t nstream = 0;          // (rxg_delivery_streams)
-        rxg_tcp_stream *h_ss_stream = nullptr;
-        rxg_ddos_summary *h_ddos = nullptr; // (rxg_delivery_ddos)
-        uint32_t nrun = 0;             // (rxg_delivery_runs)
-        uint32_t moved = 0;            // (rxg_delivery_moved)
-        rxg_tcp_run *h_ss_run = nullptr;
+        bool on = false; // submitted and not yet waited for
+        // per pass: whether it ran in this set's burst (copied at submit: the
+        // wait reads no table) and the pinned copies of its results
+        struct : udp_host { bool ran = false; } udp;
+        struct {
+            bool ran = false;
+            k4_form form{}; // the form that ran
+            rxg_segment *h_seg = nullptr;
+            uint8_t *h_payload = nullptr; // the set's own buffer (no pooled one was free)
+            uint32_t *h_totals = nullptr;
+            rxg_tcp_run *h_run = nullptr;
+            rxg_tcp_stream *h_stream = nullptr;
+            uint32_t nrun = 0, moved = 0, nstream = 0; // (the wait fills them: rxg_delivery_runs, ..)
+        } tcp;
+        struct { bool ran = false; rxg_ddos_summary *h_sum = nullptr; } ddos; // (rxg_delivery_ddos)
+        struct {
+            bool ran = false; // (rxg_delivery_cookies)
+            uint8_t *h_status = nullptr;
+            rxg_txd *h_txd = nullptr;
+            uint32_t *h_totals = nullptr;
+        } ck;
+        struct {
+            bool ran = false; // (rxg_delivery_l2)
+            uint8_t *h_status = nullptr, *h_out = nullptr;
+            uint64_t h_out_cap = 0;
+            uint32_t *h_roff = nullptr, *h_rsrc = nullptr, *h_totals = nullptr;
+            uint16_t *h_rlen = nullptr;
+        } l2;
         uint64_t ticket = 0;
         double t0 = 0, t1 = 0;
         int pl = -1; // the pooled payload buffer the library holds for this set
-        rxg_dgram *h_cp_dg = nullptr;
-        uint32_t *h_cp_first = nullptr, *h_cp_totals = nullptr;
-        uint8_t *h_cp_payload = nullptr;
-        rxg_segment *h_ss_seg = nullptr;
-        uint8_t *h_ss_payload = nullptr;
-        uint32_t *h_ss_totals = nullptr;
         hipEvent_t tev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     } dls[RXG_DELIVER_DEPTH];
     uint32_t dl_next = 0; // the set the next submit takes (round robin)
-    uint32_t *d_ss_totals = nullptr;
-    void *d_ss_ws = nullptr;
-    size_t d_ss_ws_cap = 0;
     // registered host memory (rxg_register_host): frames of an mbuf burst that
     // all lie in it are pulled by the device instead of gathered on the host
     struct host_region {
@@ -417,6 +445,55 @@ static int ensure_dev_async(void **p, size_t *cap, size_t bytes, hipStream_t s) 
     HIPCHK(hipMallocAsync(p, bytes, s));
     *cap = bytes;
     return RXG_OK;
+}
+
+#define RCCHK(x)                                                                                   \
+    do {                                                                                           \
+        int rc_ = (x);                                                                             \
+        if (rc_) return rc_;                                                                       \
+    } while (0)
+
+// A burst pass's workspace grown to `bytes` before a launch on s.  Its uses are
+// ordered by the caller (all on one stream, or event-chained), so it is freed
+// and grown in stream order.  (bytes == 0 with no buffer yet: nothing to do.)
+static int ws_grow(rxg_ctx::ws_buf &ws, size_t bytes, hipStream_t s, bool *grew = nullptr) {
+    if (grew) *grew = bytes > ws.cap; // (a new buffer: its contents are undefined)
+    return bytes <= ws.cap ? RXG_OK : ensure_dev_async(&ws.p, &ws.cap, bytes, s);
+}
+
+// First-use allocations, one pointer each: a failed call returns its error
+// with *p null, so the next call allocates exactly what is still missing.
+template <class T> static int dev_alloc(T **p, size_t bytes) {
+    const hipError_t e = *p ? hipSuccess : hipMalloc((void **)p, bytes);
+    if (e != hipSuccess) *p = nullptr;
+    return rx_set_hip_error(e);
+}
+template <class T> static int pin_alloc(T **p, size_t bytes) {
+    const hipError_t e = *p ? hipSuccess : hipHostMalloc((void **)p, bytes, 0);
+    if (e != hipSuccess) *p = nullptr;
+    return rx_set_hip_error(e);
+}
+// a device result and its pinned copy, the same size
+template <class T> static int both_alloc(T **d, T **h, size_t bytes) {
+    RCCHK(dev_alloc(d, bytes));
+    return pin_alloc(h, bytes);
+}
+static void dev_free(std::initializer_list<void *> ds) {
+    for (void *d : ds) (void)hipFree(d);
+}
+static void pin_free(std::initializer_list<void *> hs) {
+    for (void *h : hs)
+        if (h) (void)hipHostFree(h);
+}
+// a result's copy to pinned host memory, on the context's stream
+static hipError_t copy_back(rxg_ctx *c, void *h, const void *d, size_t bytes) {
+    return hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, c->stream);
+}
+static bool bad_unit(uint32_t off_unit_log2) { return off_unit_log2 < 4 || off_unit_log2 > 16; }
+// the opening of the device entry points: a context with a device
+static int dev_ctx(const rxg_ctx *c) {
+    if (!c) return RXG_EINVAL;
+    return c->device == RXG_HOST_ONLY ? RXG_ENODEV : RXG_OK;
 }
 
 // Save the calling thread's current device, switch to the context's, restore
@@ -811,6 +888,10 @@ int rxg_open(rxg_ctx **out, int device, uint32_t max_pkts, uint64_t max_bytes) {
     return RXG_OK;
 }
 
+// every buffer of a burst pass, the sets' pinned copies included (with the passes, below)
+static void udp_release(rxg_ctx *c), tcp_release(rxg_ctx *c), ddos_release(rxg_ctx *c),
+    ck_release(rxg_ctx *c), l2_release(rxg_ctx *c);
+
 void rxg_close(rxg_ctx *c) {
     if (!c) return;
     if (c->device == RXG_HOST_ONLY) {
@@ -831,60 +912,18 @@ void rxg_close(rxg_ctx *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->s_h2d) (void)hipStreamSynchronize(c->s_h2d);
     if (c->s_d2h) (void)hipStreamSynchronize(c->s_d2h);
-    (void)hipFree(c->d_udp);
-    (void)hipFree(c->d_tcp);
-    (void)hipFree(c->d_listen);
-    (void)hipFree(c->d_udp_port);
-    (void)hipFree(c->d_udpc);
-    (void)hipFree(c->d_udpw);
-    (void)hipFree(c->d_delta);
-    if (c->h_delta) (void)hipHostFree(c->h_delta);
-    (void)hipFree(c->d_counts);
-    (void)hipFree(c->d_counts_base);
-    (void)hipFree(c->d_ws);
-    (void)hipFree(c->d_aux);
-    (void)hipFree(c->d_txe);
-    (void)hipFree(c->d_cp_dg);
-    (void)hipFree(c->d_cp_first);
-    (void)hipFree(c->d_cp_payload);
-    (void)hipFree(c->d_cp_totals);
-    (void)hipFree(c->d_cp_ws);
-    (void)hipFree(c->d_ss_seg);
-    (void)hipFree(c->d_ss_payload);
-    (void)hipFree(c->d_ss_run);
-    (void)hipFree(c->d_ss_stream);
-    (void)hipFree(c->d_ss_totals);
-    (void)hipFree(c->d_ss_ws);
-    (void)hipFree(c->d_ddos_ws);
-    (void)hipFree(c->d_ddos_state);
-    (void)hipFree(c->d_ddos_sum);
-    (void)hipFree(c->d_ck_ws);
-    (void)hipFree(c->d_ck_mask);
-    (void)hipFree(c->d_ck_status);
-    (void)hipFree(c->d_ck_txd);
-    (void)hipFree(c->d_ck_totals);
-    if (c->ev_ck) (void)hipEventDestroy(c->ev_ck);
-    for (void *d : {c->d_l2_ws, (void *)c->d_l2_status, (void *)c->d_l2_out, (void *)c->d_l2_roff,
-                    (void *)c->d_l2_rlen, (void *)c->d_l2_rsrc, (void *)c->d_l2_totals})
-        (void)hipFree(d);
-    for (rxg_ctx::delivery_set &ds : c->dls) {
-        for (void *h : {(void *)ds.h_cp_dg, (void *)ds.h_cp_first, (void *)ds.h_cp_totals,
-                        (void *)ds.h_cp_payload, (void *)ds.h_ss_seg, (void *)ds.h_ss_payload,
-                        (void *)ds.h_ss_totals, (void *)ds.h_ss_run, (void *)ds.h_ss_stream,
-                        (void *)ds.h_ddos, (void *)ds.h_ck_status, (void *)ds.h_ck_txd,
-                        (void *)ds.h_ck_totals, (void *)ds.h_l2_status, (void *)ds.h_l2_out,
-                        (void *)ds.h_l2_roff, (void *)ds.h_l2_rlen, (void *)ds.h_l2_rsrc,
-                        (void *)ds.h_l2_totals})
-            if (h) (void)hipHostFree(h);
+    dev_free({c->d_udp, c->d_tcp, c->d_listen, c->d_udp_port, c->d_udpc, c->d_udpw, c->d_delta,
+              c->d_counts, c->d_counts_base, c->d_ws, c->d_aux, c->d_txe});
+    pin_free({c->h_delta});
+    udp_release(c);
+    tcp_release(c);
+    ddos_release(c);
+    ck_release(c);
+    l2_release(c);
+    for (rxg_ctx::delivery_set &ds : c->dls)
         for (hipEvent_t e : ds.tev)
             if (e) (void)hipEventDestroy(e);
-    }
-    for (rxg_ctx::pl_buf &b : c->pl)
-        if (b.h) (void)hipHostFree(b.h);
-    if (c->h_cp_dg) (void)hipHostFree(c->h_cp_dg);
-    if (c->h_cp_first) (void)hipHostFree(c->h_cp_first);
-    if (c->h_cp_payload) (void)hipHostFree(c->h_cp_payload);
-    if (c->h_cp_totals) (void)hipHostFree(c->h_cp_totals);
+    for (rxg_ctx::pl_buf &b : c->pl) pin_free({b.h});
     for (rxg_ctx::ws_use &u : c->wu)
         if (u.ev) (void)hipEventDestroy(u.ev);
     for (rx_track &t : c->trk)
@@ -893,15 +932,8 @@ void rxg_close(rxg_ctx *c) {
     if (c->ev_k1) (void)hipEventDestroy(c->ev_k1);
     if (c->ev_aux) (void)hipEventDestroy(c->ev_aux);
     for (rxg_ctx::slot &sl : c->slots) {
-        (void)hipFree(sl.d_pkts);
-        (void)hipFree(sl.d_off);
-        (void)hipFree(sl.d_len);
-        (void)hipFree(sl.d_out);
-        if (sl.h_stage) (void)hipHostFree(sl.h_stage);
-        if (sl.h_off) (void)hipHostFree(sl.h_off);
-        if (sl.h_len) (void)hipHostFree(sl.h_len);
-        if (sl.h_src) (void)hipHostFree(sl.h_src);
-        (void)hipFree(sl.d_src);
+        dev_free({sl.d_pkts, sl.d_off, sl.d_len, sl.d_out, sl.d_src});
+        pin_free({sl.h_stage, sl.h_off, sl.h_len, sl.h_src});
         if (sl.ev_in) (void)hipEventDestroy(sl.ev_in);
         if (sl.ev_k) (void)hipEventDestroy(sl.ev_k);
         if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
@@ -1283,19 +1315,19 @@ int rxg_tune_deliver(rxg_ctx *c, uint32_t flags) {
 
 int rxg_tune_ddos(rxg_ctx *c, uint32_t lanes_per_frame) {
     if (!c || (lanes_per_frame && !rx_ddos_has_g(lanes_per_frame))) return RXG_EINVAL;
-    c->tune_ddos = lanes_per_frame;
+    c->ddos.lanes = lanes_per_frame;
     return RXG_OK;
 }
 
 int rxg_tune_ddos_thresh(rxg_ctx *c, double thresh) {
     if (!c || thresh != thresh) return RXG_EINVAL;
-    c->ddos_thresh = thresh;
+    c->ddos.thresh = thresh;
     return RXG_OK;
 }
 
 int rxg_tune_gro(rxg_ctx *c, uint32_t W) {
     if (!c || W > RXG_GRO_MAX_WINDOW) return RXG_EINVAL;
-    c->gro_window = W ? W : RXG_GRO_DEFAULT_WINDOW;
+    c->tcp.window = W ? W : RXG_GRO_DEFAULT_WINDOW;
     return RXG_OK;
 }
 
@@ -1491,11 +1523,10 @@ static int classify_dev_impl(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *
                              const uint16_t *d_len, uint32_t n, uint32_t off_unit_log2,
                              uint32_t len_hint, void *d_out, uint64_t *d_counts, hipStream_t s,
                              hipStream_t cs, uint32_t v8 = 0) {
-    if (!c) return RXG_EINVAL;
-    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
+    RCCHK(dev_ctx(c));
     if (n == 0) return RXG_OK;
     if (!d_pkts || !d_off || !d_len || !d_out) return RXG_EINVAL;
-    if (off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
+    if (bad_unit(off_unit_log2)) return RXG_EINVAL;
     DEVGUARD(c);
     uint32_t g = c->tune_g, p = c->tune_p, fpg = c->tune_fpg, pipe = c->tune_pipe;
     if (!g && pipe == ~0u) rx_pick_variant(len_hint, &g, &p, &fpg, &pipe, v8 != 0);
@@ -1576,10 +1607,9 @@ static int submit_slot(rxg_ctx *c, rxg_ctx::slot &sl, const uint8_t *pkts, uint6
 
 static int check_host_burst(rxg_ctx *c, const uint8_t *pkts, uint64_t span_bytes, const uint32_t *off,
                             const uint16_t *len, uint32_t n, uint32_t off_unit_log2) {
-    if (!c) return RXG_EINVAL;
-    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
+    RCCHK(dev_ctx(c));
     if (!pkts || !off || !len) return RXG_EINVAL;
-    if (off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
+    if (bad_unit(off_unit_log2)) return RXG_EINVAL;
     if (n > c->max_pkts || !c->slots[0].d_pkts) return RXG_ERANGE;
     if (((span_bytes + 15) & ~15ull) > c->max_bytes) return RXG_ERANGE;
     return RXG_OK;
@@ -1602,8 +1632,7 @@ int rxg_submit(rxg_ctx *c, const uint8_t *pkts, uint64_t span_bytes, const uint3
 }
 
 int rxg_wait(rxg_ctx *c, uint64_t ticket) {
-    if (!c) return RXG_EINVAL;
-    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
+    RCCHK(dev_ctx(c));
     if (ticket == 0) return RXG_OK; // empty burst
     if (ticket >= c->next_ticket) return RXG_EINVAL;
     const rxg_ctx::slot &sl = c->slots[ticket % RXG_PIPE_DEPTH];
@@ -1623,11 +1652,10 @@ int rxg_classify_span(rxg_ctx *c, const uint8_t *pkts, uint64_t span_bytes, cons
 
 int rxg_classify(rxg_ctx *c, const uint8_t *pkts, const uint32_t *off, const uint16_t *len,
                  uint32_t n, uint32_t off_unit_log2, rxg_verdict *out) {
-    if (!c) return RXG_EINVAL;
-    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
+    RCCHK(dev_ctx(c));
     if (n == 0) return RXG_OK;
     if (!pkts || !off || !len || !out) return RXG_EINVAL;
-    if (off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
+    if (bad_unit(off_unit_log2)) return RXG_EINVAL;
     uint64_t span = 0;
     for (uint32_t i = 0; i < n; ++i) {
         const uint64_t e = ((uint64_t)off[i] << off_unit_log2) + len[i];
@@ -1750,8 +1778,7 @@ static int gather_mbufs(rxg_ctx *c, rxg_ctx::slot &sl, rxg_mbuf *const *m, uint3
 }
 
 int rxg_process_mbufs(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *out) {
-    if (!c) return RXG_EINVAL;
-    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
+    RCCHK(dev_ctx(c));
     if (n == 0) return RXG_OK;
     if (!m || !out) return RXG_EINVAL;
     if (n > c->max_pkts || !c->slots[0].h_stage) return RXG_ERANGE;
@@ -1765,19 +1792,37 @@ int rxg_process_mbufs(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *o
     return rc ? rc : rxg_wait(c, t);
 }
 
-static int compact_impl(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off,
-                        const uint16_t *d_len, uint32_t n, uint32_t off_unit_log2,
-                        const uint4 *d_v, rxg_dgram *d_dg, uint32_t *d_first, uint8_t *d_payload,
-                        uint64_t cap, uint32_t *d_totals, hipStream_t s) {
+// ---- the burst passes behind the classify: K3, K4, K6, K7, K8 ---------------
+// Each pass has a launch wrapper (its workspace grown on the call's stream, then
+// the kernels), its public rxg_*_dev entry points, and four steps of the same
+// shape for the delivery pipeline (rxg_deliver_submit), which a new pass adds
+// beside its structs in rxg_ctx and delivery_set and its accessor:
+//   <pass>_reserve   first-use / grow allocations, the context's and the set's
+//   <pass>_enqueue   the launch on c->stream
+//   <pass>_copy_out  the copies into the set, upper-bound sizes
+//   <pass>_release   every buffer of the pass (rxg_close)
+
+// a burst on the device as every pass reads it
+struct burst_view {
+    const uint8_t *d_pkts; const uint32_t *d_off; const uint16_t *d_len;
+    uint32_t n, ul;      // frames; the offset unit (log2 bytes)
+    const uint4 *d_out;  // K1's verdicts
+    uint64_t span, pos;  // (staged bursts) bytes staged; bound of the 16-B padded payloads
+};
+static burst_view view_of(const uint8_t *d_pkts, const uint32_t *d_off, const uint16_t *d_len,
+                          uint32_t n, uint32_t ul, const rxg_verdict *d_v) {
+    return burst_view{d_pkts, d_off, d_len, n, ul, reinterpret_cast<const uint4 *>(d_v), 0, 0};
+}
+typedef rxg_ctx::delivery_set dset;
+
+// ---- UDP compaction (K3) ---------------------------------------------------
+static int udp_launch(rxg_ctx *c, const burst_view &b, rxg_dgram *d_dg, uint32_t *d_first,
+                      uint8_t *d_payload, uint64_t cap, uint32_t *d_totals, hipStream_t s) {
     const uint32_t nf = c->fs.udp.id_space();
     if (nf == 0 || nf > RXG_COMPACT_MAX_FLOWS) return nf ? RXG_ERANGE : RXG_OK;
-    const size_t ws = rx_compact_ws_bytes(n, nf);
-    if (ws > c->d_cp_ws_cap) { // (its uses are all on s: freed and grown in stream order)
-        int rc = ensure_dev_async(&c->d_cp_ws, &c->d_cp_ws_cap, ws, s);
-        if (rc) return rc;
-    }
-    HIPCHK(rx_compact_launch(d_pkts, d_off, d_len, n, off_unit_log2, d_v, nf, d_dg, d_first,
-                             d_payload, cap, d_totals, c->d_cp_ws, s));
+    RCCHK(ws_grow(c->udp.ws, rx_compact_ws_bytes(b.n, nf), s));
+    HIPCHK(rx_compact_launch(b.d_pkts, b.d_off, b.d_len, b.n, b.ul, b.d_out, nf, d_dg, d_first,
+                             d_payload, cap, d_totals, c->udp.ws.p, s));
     return RXG_OK;
 }
 
@@ -1785,24 +1830,59 @@ int rxg_udp_compact_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off
                         const uint16_t *d_len, uint32_t n, uint32_t off_unit_log2,
                         const rxg_verdict *d_v, rxg_dgram *d_dgram, uint32_t *d_first,
                         uint8_t *d_payload, uint64_t payload_cap, uint32_t *d_totals, void *stream) {
-    if (!c) return RXG_EINVAL;
-    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
+    RCCHK(dev_ctx(c));
     if (!d_first || !d_totals || (n && (!d_pkts || !d_off || !d_len || !d_v || !d_dgram ||
                                         !d_payload)))
         return RXG_EINVAL;
-    if (off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
+    if (bad_unit(off_unit_log2)) return RXG_EINVAL;
     DEVGUARD(c);
     if (c->fs.udp.id_space() > RXG_COMPACT_MAX_FLOWS) return RXG_ERANGE;
-    if (c->fs.udp.id_space() == 0) { // no UDP ids: nothing is delivered (compact_impl writes nothing)
+    if (c->fs.udp.id_space() == 0) { // no UDP ids: nothing is delivered (udp_launch writes nothing)
         HIPCHK(hipMemsetAsync(d_totals, 0, 3 * sizeof(uint32_t), (hipStream_t)stream));
         HIPCHK(hipMemsetAsync(d_first, 0, sizeof(uint32_t), (hipStream_t)stream));
         return RXG_OK;
     }
-    return compact_impl(c, d_pkts, d_off, d_len, n, off_unit_log2,
-                        reinterpret_cast<const uint4 *>(d_v), d_dgram, d_first, d_payload,
-                        payload_cap, d_totals, (hipStream_t)stream);
+    return udp_launch(c, view_of(d_pkts, d_off, d_len, n, off_unit_log2, d_v), d_dgram, d_first,
+                      d_payload, payload_cap, d_totals, (hipStream_t)stream);
 }
 
+// The device results, sized for a full staging slot, and one group of pinned
+// copies of them: a delivery set's, or the context's own (rxg_process_mbufs_udp).
+static int udp_reserve(rxg_ctx *c, rxg_ctx::udp_host &h) {
+    rxg_ctx::udp_pass &u = c->udp;
+    const size_t dg = (size_t)c->max_pkts * sizeof(rxg_dgram), first = (RXG_COMPACT_MAX_FLOWS + 1) * 4;
+    RCCHK(both_alloc(&u.d_dg, &h.h_dg, dg));
+    RCCHK(both_alloc(&u.d_first, &h.h_first, first));
+    RCCHK(both_alloc(&u.d_payload, &h.h_payload, c->max_bytes));
+    return both_alloc(&u.d_totals, &h.h_totals, 4 * sizeof(uint32_t));
+}
+static int udp_enqueue(rxg_ctx *c, const burst_view &b) {
+    return udp_launch(c, b, c->udp.d_dg, c->udp.d_first, c->udp.d_payload, c->max_bytes,
+                      c->udp.d_totals, c->stream);
+}
+// nf: the UDP id space (first[] has nf + 1 entries)
+static int udp_copy_out(rxg_ctx *c, dset &ds, const burst_view &b, uint32_t nf) {
+    const rxg_ctx::udp_pass &u = c->udp;
+    HIPCHK(copy_back(c, ds.udp.h_totals, u.d_totals, 3 * sizeof(uint32_t)));
+    HIPCHK(copy_back(c, ds.udp.h_first, u.d_first, (nf + 1) * sizeof(uint32_t)));
+    HIPCHK(copy_back(c, ds.udp.h_dg, u.d_dg, (size_t)b.n * sizeof(rxg_dgram)));
+    HIPCHK(copy_back(c, ds.udp.h_payload, u.d_payload, b.pos));
+    return RXG_OK;
+}
+static void udp_release(rxg_ctx *c) {
+    rxg_ctx::udp_pass &u = c->udp;
+    dev_free({u.d_dg, u.d_first, u.d_payload, u.d_totals, u.ws.p});
+    pin_free({u.own.h_dg, u.own.h_first, u.own.h_payload, u.own.h_totals});
+    for (dset &ds : c->dls) pin_free({ds.udp.h_dg, ds.udp.h_first, ds.udp.h_payload, ds.udp.h_totals});
+}
+
+// the staged burst of a slot
+static burst_view slot_view(const rxg_ctx::slot &sl, const staged &st, uint32_t n) {
+    return burst_view{sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, sl.d_out, st.span, st.bound};
+}
+
+// K1 + K3 of an mbuf burst with the context's own pinned copies (no delivery
+// set): exact-size copies out, at the price of two synchronisations
 int rxg_process_mbufs_udp(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *out,
                           const rxg_dgram **dgram, const uint32_t **first, const uint8_t **payload,
                           uint32_t *ndgram, uint64_t *nbytes) {
@@ -1815,64 +1895,149 @@ int rxg_process_mbufs_udp(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdic
     const uint32_t nf = c->fs.udp.id_space();
     if (nf > RXG_COMPACT_MAX_FLOWS) return RXG_ERANGE;
     DEVGUARD(c);
-    if (!c->h_cp_totals) { // first use: results sized for a full staging slot
-        // (h_cp_totals is set last: a failed allocation leaves the set
-        // incomplete and the next call retries the missing pieces)
-        if (!c->d_cp_dg) HIPCHK(hipMalloc(&c->d_cp_dg, (size_t)c->max_pkts * sizeof(rxg_dgram)));
-        if (!c->d_cp_first)
-            HIPCHK(hipMalloc(&c->d_cp_first, (RXG_COMPACT_MAX_FLOWS + 1) * sizeof(uint32_t)));
-        if (!c->d_cp_payload) HIPCHK(hipMalloc(&c->d_cp_payload, c->max_bytes));
-        if (!c->d_cp_totals) HIPCHK(hipMalloc(&c->d_cp_totals, 4 * sizeof(uint32_t)));
-        if (!c->h_cp_dg)
-            HIPCHK(hipHostMalloc((void **)&c->h_cp_dg, (size_t)c->max_pkts * sizeof(rxg_dgram), 0));
-        if (!c->h_cp_first)
-            HIPCHK(hipHostMalloc((void **)&c->h_cp_first,
-                                 (RXG_COMPACT_MAX_FLOWS + 1) * sizeof(uint32_t), 0));
-        if (!c->h_cp_payload) HIPCHK(hipHostMalloc((void **)&c->h_cp_payload, c->max_bytes, 0));
-        HIPCHK(hipHostMalloc((void **)&c->h_cp_totals, 4 * sizeof(uint32_t), 0));
-    }
-    *dgram = c->h_cp_dg;
-    *first = c->h_cp_first;
-    *payload = c->h_cp_payload;
-    memset(c->h_cp_first, 0, (nf + 1) * sizeof(uint32_t));
+    const rxg_ctx::udp_pass &u = c->udp;
+    rxg_ctx::udp_host &h = c->udp.own;
+    RCCHK(udp_reserve(c, h));
+    *dgram = h.h_dg, *first = h.h_first, *payload = h.h_payload;
+    memset(h.h_first, 0, (nf + 1) * sizeof(uint32_t));
     if (n == 0) return RXG_OK;
     const uint64_t t = c->next_ticket++;
     rxg_ctx::slot &sl = c->slots[t % RXG_PIPE_DEPTH];
     staged st;
-    int rc = gather_mbufs(c, sl, m, n, &st, true);
-    if (rc) return rc;
-    rc = submit_slot(c, sl, st.src, st.span, sl.h_off, sl.h_len, n, st.ul, out, t, st.pulled);
-    if (rc) return rc;
+    RCCHK(gather_mbufs(c, sl, m, n, &st, true));
+    RCCHK(submit_slot(c, sl, st.src, st.span, sl.h_off, sl.h_len, n, st.ul, out, t, st.pulled));
     // the compaction follows the classify on the context's stream (its inputs:
     // the staged frames and the device verdicts of this slot)
-    rc = compact_impl(c, sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, sl.d_out, c->d_cp_dg, c->d_cp_first,
-                      c->d_cp_payload, c->max_bytes, c->d_cp_totals, c->stream);
-    if (rc) return rc;
+    RCCHK(udp_enqueue(c, slot_view(sl, st, n)));
     if (nf) {
-        HIPCHK(hipMemcpyAsync(c->h_cp_totals, c->d_cp_totals, 3 * sizeof(uint32_t),
-                              hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(copy_back(c, h.h_totals, u.d_totals, 3 * sizeof(uint32_t)));
         HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->h_cp_totals[2]) return RXG_ERANGE; // (not reached: staging bounds the payloads)
-        *ndgram = c->h_cp_totals[0];
-        *nbytes = c->h_cp_totals[1];
-        HIPCHK(hipMemcpyAsync(c->h_cp_first, c->d_cp_first, (nf + 1) * sizeof(uint32_t),
-                              hipMemcpyDeviceToHost, c->stream));
-        if (*ndgram)
-            HIPCHK(hipMemcpyAsync(c->h_cp_dg, c->d_cp_dg, (size_t)*ndgram * sizeof(rxg_dgram),
-                                  hipMemcpyDeviceToHost, c->stream));
-        if (*nbytes)
-            HIPCHK(hipMemcpyAsync(c->h_cp_payload, c->d_cp_payload, *nbytes, hipMemcpyDeviceToHost,
-                                  c->stream));
+        if (h.h_totals[2]) return RXG_ERANGE; // (not reached: staging bounds the payloads)
+        *ndgram = h.h_totals[0];
+        *nbytes = h.h_totals[1];
+        HIPCHK(copy_back(c, h.h_first, u.d_first, (nf + 1) * sizeof(uint32_t)));
+        if (*ndgram) HIPCHK(copy_back(c, h.h_dg, u.d_dg, (size_t)*ndgram * sizeof(rxg_dgram)));
+        if (*nbytes) HIPCHK(copy_back(c, h.h_payload, u.d_payload, *nbytes));
         HIPCHK(hipStreamSynchronize(c->stream));
     }
     return rxg_wait(c, t);
 }
 
-// K4's workspace (rx_segsort.hip: one buffer for all four forms) grown to
-// bytes; its uses are all on s, so it is freed and grown in stream order
-static int k4_ws_grow(rxg_ctx *c, size_t bytes, hipStream_t s) {
-    if (bytes <= c->d_ss_ws_cap) return RXG_OK;
-    return ensure_dev_async(&c->d_ss_ws, &c->d_ss_ws_cap, bytes, s);
+// ---- TCP segment sort + payload gather (K4 and its forms) --------------------
+// form f on s; W: the window of the forms that take one (order: 0 = no coalescing)
+static int tcp_launch(rxg_ctx *c, const k4_form &f, const burst_view &b, uint32_t W, rxg_segment *seg,
+                      rxg_tcp_run *run, rxg_tcp_stream *stream, uint8_t *payload, uint64_t cap,
+                      uint32_t *totals, hipStream_t s) {
+    rxg_ctx::tcp_pass &t = c->tcp;
+    const uint32_t nt = c->fs.tcp.id_space();
+    RCCHK(ws_grow(t.ws, f.ws_bytes(b.n), s));
+    if (f.assemble)
+        HIPCHK(rx_assemble_launch(b.d_pkts, b.d_off, b.d_len, b.n, b.ul, b.d_out, nt, seg, stream,
+                                  payload, cap, totals, t.ws.p, s));
+    else if (f.order)
+        HIPCHK(rx_order_launch(b.d_pkts, b.d_off, b.d_len, b.n, b.ul, b.d_out, nt, W, seg, run, payload,
+                               cap, totals, t.ws.p, s));
+    else if (f.gro)
+        HIPCHK(rx_gro_launch(b.d_pkts, b.d_off, b.d_len, b.n, b.ul, b.d_out, nt, W, seg, run, payload,
+                             cap, totals, t.ws.p, s));
+    else
+        HIPCHK(rx_segsort_launch(b.d_pkts, b.d_off, b.d_len, b.n, b.ul, b.d_out, nt, seg, payload, cap,
+                                 totals, t.ws.p, s));
+    return RXG_OK;
+}
+
+int rxg_tcp_compact_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off,
+                        const uint16_t *d_len, uint32_t n, uint32_t off_unit_log2,
+                        const rxg_verdict *d_v, rxg_segment *d_seg, uint8_t *d_payload,
+                        uint64_t payload_cap, uint32_t *d_totals, void *stream) {
+    RCCHK(dev_ctx(c));
+    if (!d_totals || (n && (!d_pkts || !d_off || !d_len || !d_v || !d_seg)))
+        return RXG_EINVAL; // (d_payload null: records only, RXG_DLV_TCP_IN_PLACE)
+    if (bad_unit(off_unit_log2)) return RXG_EINVAL;
+    DEVGUARD(c);
+    return tcp_launch(c, k4_form{}, view_of(d_pkts, d_off, d_len, n, off_unit_log2, d_v), 0, d_seg,
+                      nullptr, nullptr, d_payload, payload_cap, d_totals, (hipStream_t)stream);
+}
+
+int rxg_tcp_coalesce_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off,
+                         const uint16_t *d_len, uint32_t n, uint32_t off_unit_log2,
+                         const rxg_verdict *d_v, uint32_t W, rxg_segment *d_seg, rxg_tcp_run *d_run,
+                         uint8_t *d_payload, uint64_t payload_cap, uint32_t *d_totals, void *stream) {
+    RCCHK(dev_ctx(c));
+    if (!d_totals || !d_payload || (n && (!d_pkts || !d_off || !d_len || !d_v || !d_seg || !d_run)))
+        return RXG_EINVAL;
+    if (W < 1u || W > RXG_GRO_MAX_WINDOW) return RXG_EINVAL;
+    if (bad_unit(off_unit_log2)) return RXG_EINVAL;
+    DEVGUARD(c);
+    return tcp_launch(c, k4_form::of(RXG_DLV_TCP_GRO), view_of(d_pkts, d_off, d_len, n, off_unit_log2, d_v),
+                      W, d_seg, d_run, nullptr, d_payload, payload_cap, d_totals, (hipStream_t)stream);
+}
+
+int rxg_tcp_compact_ordered_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off,
+                                const uint16_t *d_len, uint32_t n, uint32_t off_unit_log2,
+                                const rxg_verdict *d_v, uint32_t W, rxg_segment *d_seg,
+                                rxg_tcp_run *d_run, uint8_t *d_payload, uint64_t payload_cap,
+                                uint32_t *d_totals, void *stream) {
+    RCCHK(dev_ctx(c));
+    if (!d_totals || (n && (!d_pkts || !d_off || !d_len || !d_v || !d_seg))) return RXG_EINVAL;
+    // (W == 0: K4's rules, d_payload null = records only; else the coalescing call's)
+    if (W > RXG_GRO_MAX_WINDOW || (W && (!d_payload || (n && !d_run)))) return RXG_EINVAL;
+    if (bad_unit(off_unit_log2)) return RXG_EINVAL;
+    DEVGUARD(c);
+    return tcp_launch(c, k4_form::of(RXG_DLV_TCP_ORDER | (W ? RXG_DLV_TCP_GRO : 0u)),
+                      view_of(d_pkts, d_off, d_len, n, off_unit_log2, d_v), W, d_seg, d_run, nullptr,
+                      d_payload, payload_cap, d_totals, (hipStream_t)stream);
+}
+
+int rxg_tcp_assemble_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off,
+                         const uint16_t *d_len, uint32_t n, uint32_t off_unit_log2,
+                         const rxg_verdict *d_v, rxg_segment *d_seg, rxg_tcp_stream *d_stream,
+                         uint8_t *d_payload, uint64_t payload_cap, uint32_t *d_totals, void *stream) {
+    RCCHK(dev_ctx(c));
+    if (!d_totals || !d_payload) return RXG_EINVAL;
+    if (n && (!d_pkts || !d_off || !d_len || !d_v || !d_seg || !d_stream)) return RXG_EINVAL;
+    if (bad_unit(off_unit_log2)) return RXG_EINVAL;
+    DEVGUARD(c);
+    return tcp_launch(c, k4_form::of(RXG_DLV_TCP_ASSEMBLE), view_of(d_pkts, d_off, d_len, n, off_unit_log2, d_v),
+                      0, d_seg, nullptr, d_stream, d_payload, payload_cap, d_totals, (hipStream_t)stream);
+}
+
+// (whatever the tables hold: rxg_delivery.seg is never null; the runs and streams with the
+// first burst of their form; the payload's host side: deliver_pick_payload)
+static int tcp_reserve(rxg_ctx *c, dset &ds, const k4_form &f) {
+    rxg_ctx::tcp_pass &t = c->tcp;
+    const size_t n = c->max_pkts;
+    RCCHK(both_alloc(&t.d_seg, &ds.tcp.h_seg, n * sizeof(rxg_segment)));
+    RCCHK(both_alloc(&t.d_totals, &ds.tcp.h_totals, 6 * sizeof(uint32_t)));
+    RCCHK(dev_alloc(&t.d_payload, c->max_bytes));
+    if (f.assemble) RCCHK(both_alloc(&t.d_stream, &ds.tcp.h_stream, n * sizeof(rxg_tcp_stream)));
+    if (f.gro) RCCHK(both_alloc(&t.d_run, &ds.tcp.h_run, n * sizeof(rxg_tcp_run)));
+    return RXG_OK;
+}
+// (rxg_tune_deliver refuses in place with coalescing or assembly: those get the buffer, as before)
+static int tcp_enqueue(rxg_ctx *c, const k4_form &f, const burst_view &b) {
+    rxg_ctx::tcp_pass &t = c->tcp;
+    return tcp_launch(c, f, b, f.gro ? t.window : 0u, t.d_seg, t.d_run, t.d_stream,
+                      f.inplace ? nullptr : t.d_payload, c->max_bytes, t.d_totals, c->stream);
+}
+// h_payload: where this burst's payloads go (null in place: none is copied back)
+static int tcp_copy_out(rxg_ctx *c, dset &ds, const k4_form &f, const burst_view &b, uint8_t *h_payload) {
+    const rxg_ctx::tcp_pass &t = c->tcp;
+    HIPCHK(copy_back(c, ds.tcp.h_totals, t.d_totals, f.ntotals() * sizeof(uint32_t)));
+    if (f.assemble) // (the streams cross with the records: at most n of them)
+        HIPCHK(copy_back(c, ds.tcp.h_stream, t.d_stream, (size_t)b.n * sizeof(rxg_tcp_stream)));
+    if (f.gro) // (the runs cross with the records: at most n of them)
+        HIPCHK(copy_back(c, ds.tcp.h_run, t.d_run, (size_t)b.n * sizeof(rxg_tcp_run)));
+    HIPCHK(copy_back(c, ds.tcp.h_seg, t.d_seg, (size_t)b.n * sizeof(rxg_segment)));
+    if (h_payload)
+        HIPCHK(copy_back(c, h_payload, t.d_payload, b.pos));
+    return RXG_OK;
+}
+static void tcp_release(rxg_ctx *c) {
+    rxg_ctx::tcp_pass &t = c->tcp;
+    dev_free({t.d_seg, t.d_payload, t.d_run, t.d_stream, t.d_totals, t.ws.p});
+    for (dset &ds : c->dls)
+        pin_free({ds.tcp.h_seg, ds.tcp.h_payload, ds.tcp.h_totals, ds.tcp.h_run, ds.tcp.h_stream});
 }
 
 int rxg_payload_hold(rxg_ctx *c, int32_t ref) {
@@ -1887,76 +2052,16 @@ int rxg_payload_release(rxg_ctx *c, int32_t ref) {
     return RXG_OK;
 }
 
-int rxg_tcp_compact_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off,
-                        const uint16_t *d_len, uint32_t n, uint32_t off_unit_log2,
-                        const rxg_verdict *d_v, rxg_segment *d_seg, uint8_t *d_payload,
-                        uint64_t payload_cap, uint32_t *d_totals, void *stream) {
-    if (!c) return RXG_EINVAL;
-    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
-    if (!d_totals || (n && (!d_pkts || !d_off || !d_len || !d_v || !d_seg)))
-        return RXG_EINVAL; // (d_payload null: records only, RXG_DLV_TCP_IN_PLACE)
-    if (off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
-    DEVGUARD(c);
-    const int rc = k4_ws_grow(c, rx_segsort_ws_bytes(n), (hipStream_t)stream);
-    if (rc) return rc;
-    HIPCHK(rx_segsort_launch(d_pkts, d_off, d_len, n, off_unit_log2, reinterpret_cast<const uint4 *>(d_v),
-                             c->fs.tcp.id_space(), d_seg, d_payload, payload_cap, d_totals, c->d_ss_ws,
-                             (hipStream_t)stream));
-    return RXG_OK;
-}
-
-int rxg_tcp_coalesce_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off,
-                         const uint16_t *d_len, uint32_t n, uint32_t off_unit_log2,
-                         const rxg_verdict *d_v, uint32_t W, rxg_segment *d_seg, rxg_tcp_run *d_run,
-                         uint8_t *d_payload, uint64_t payload_cap, uint32_t *d_totals, void *stream) {
-    if (!c) return RXG_EINVAL;
-    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
-    if (!d_totals || !d_payload || (n && (!d_pkts || !d_off || !d_len || !d_v || !d_seg || !d_run)))
-        return RXG_EINVAL;
-    if (W < 1u || W > RXG_GRO_MAX_WINDOW) return RXG_EINVAL;
-    if (off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
-    DEVGUARD(c);
-    const int rc = k4_ws_grow(c, rx_gro_ws_bytes(n), (hipStream_t)stream);
-    if (rc) return rc;
-    HIPCHK(rx_gro_launch(d_pkts, d_off, d_len, n, off_unit_log2, reinterpret_cast<const uint4 *>(d_v),
-                         c->fs.tcp.id_space(), W, d_seg, d_run, d_payload, payload_cap, d_totals,
-                         c->d_ss_ws, (hipStream_t)stream));
-    return RXG_OK;
-}
-
-int rxg_tcp_compact_ordered_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off,
-                                const uint16_t *d_len, uint32_t n, uint32_t off_unit_log2,
-                                const rxg_verdict *d_v, uint32_t W, rxg_segment *d_seg,
-                                rxg_tcp_run *d_run, uint8_t *d_payload, uint64_t payload_cap,
-                                uint32_t *d_totals, void *stream) {
-    if (!c) return RXG_EINVAL;
-    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
-    if (!d_totals || (n && (!d_pkts || !d_off || !d_len || !d_v || !d_seg))) return RXG_EINVAL;
-    // (W == 0: K4's rules, d_payload null = records only; else the coalescing call's)
-    if (W > RXG_GRO_MAX_WINDOW || (W && (!d_payload || (n && !d_run)))) return RXG_EINVAL;
-    if (off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
-    DEVGUARD(c);
-    const int rc = k4_ws_grow(c, rx_order_ws_bytes(n), (hipStream_t)stream);
-    if (rc) return rc;
-    HIPCHK(rx_order_launch(d_pkts, d_off, d_len, n, off_unit_log2, reinterpret_cast<const uint4 *>(d_v),
-                           c->fs.tcp.id_space(), W, d_seg, d_run, d_payload, payload_cap, d_totals,
-                           c->d_ss_ws, (hipStream_t)stream));
-    return RXG_OK;
-}
-
-// the detector's three launches on s; the context's workspace is grown first
-static int ddos_impl(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off, const uint16_t *d_len,
-                     uint32_t n, uint32_t off_unit_log2, uint32_t len_hint, double thresh,
-                     rxg_ddos_state *d_state, uint32_t *d_bits, uint8_t *d_flag, double *d_stat,
-                     rxg_ddos_summary *d_sum, hipStream_t s) {
-    const size_t ws = rx_ddos_ws_bytes(n, d_bits == nullptr);
-    if (ws > c->d_ddos_ws_cap) { // (its uses are ordered by the caller: freed and grown in stream order)
-        int rc = ensure_dev_async(&c->d_ddos_ws, &c->d_ddos_ws_cap, ws, s);
-        if (rc) return rc;
-    }
-    const uint32_t g = c->tune_ddos ? c->tune_ddos : rx_ddos_auto_g(len_hint);
-    HIPCHK(rx_ddos_launch(d_pkts, d_off, d_len, n, off_unit_log2, g, thresh, d_state, d_bits, d_flag,
-                          d_stat, d_sum, c->d_ddos_ws, s));
+// ---- the entropy flood detector (K6) -----------------------------------------
+// the detector's three launches on s
+static int ddos_launch(rxg_ctx *c, const burst_view &b, uint32_t len_hint, double thresh,
+                       rxg_ddos_state *d_state, uint32_t *d_bits, uint8_t *d_flag, double *d_stat,
+                       rxg_ddos_summary *d_sum, hipStream_t s) {
+    rxg_ctx::ddos_pass &k = c->ddos;
+    RCCHK(ws_grow(k.ws, rx_ddos_ws_bytes(b.n, d_bits == nullptr), s));
+    const uint32_t g = k.lanes ? k.lanes : rx_ddos_auto_g(len_hint);
+    HIPCHK(rx_ddos_launch(b.d_pkts, b.d_off, b.d_len, b.n, b.ul, g, thresh, d_state, d_bits, d_flag,
+                          d_stat, d_sum, k.ws.p, s));
     return RXG_OK;
 }
 
@@ -1964,24 +2069,22 @@ int rxg_ddos_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off, const
                  uint32_t n, uint32_t off_unit_log2, uint32_t len_hint, double thresh,
                  rxg_ddos_state *d_state, uint32_t *d_bits, uint8_t *d_flag, double *d_stat,
                  rxg_ddos_summary *d_summary, void *stream) {
-    if (!c) return RXG_EINVAL;
-    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
+    RCCHK(dev_ctx(c));
     if (!d_state || !d_summary || (n && (!d_pkts || !d_off || !d_len))) return RXG_EINVAL;
-    if (thresh != thresh || off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
+    if (thresh != thresh || bad_unit(off_unit_log2)) return RXG_EINVAL;
     DEVGUARD(c);
-    return ddos_impl(c, d_pkts, d_off, d_len, n, off_unit_log2, len_hint, thresh, d_state, d_bits,
-                     d_flag, d_stat, d_summary, (hipStream_t)stream);
+    return ddos_launch(c, view_of(d_pkts, d_off, d_len, n, off_unit_log2, nullptr), len_hint, thresh,
+                       d_state, d_bits, d_flag, d_stat, d_summary, (hipStream_t)stream);
 }
 
 int rxg_ddos_bits_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off, const uint16_t *d_len,
                       uint32_t n, uint32_t off_unit_log2, uint32_t len_hint, uint32_t *d_bits,
                       void *stream) {
-    if (!c) return RXG_EINVAL;
-    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
+    RCCHK(dev_ctx(c));
     if (n && (!d_pkts || !d_off || !d_len || !d_bits)) return RXG_EINVAL;
-    if (off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
+    if (bad_unit(off_unit_log2)) return RXG_EINVAL;
     DEVGUARD(c);
-    const uint32_t g = c->tune_ddos ? c->tune_ddos : rx_ddos_auto_g(len_hint);
+    const uint32_t g = c->ddos.lanes ? c->ddos.lanes : rx_ddos_auto_g(len_hint);
     HIPCHK(rx_ddos_bits_launch(d_pkts, d_off, d_len, n, off_unit_log2, g, d_bits, (hipStream_t)stream));
     return RXG_OK;
 }
@@ -1989,88 +2092,63 @@ int rxg_ddos_bits_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off, 
 int rxg_ddos_window_dev(rxg_ctx *c, const uint32_t *d_bits, const uint16_t *d_len, uint32_t n,
                         double thresh, rxg_ddos_state *d_state, uint8_t *d_flag, double *d_stat,
                         rxg_ddos_summary *d_summary, void *stream) {
-    if (!c) return RXG_EINVAL;
-    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
+    RCCHK(dev_ctx(c));
     if (!d_state || !d_summary || (n && (!d_bits || !d_len)) || thresh != thresh) return RXG_EINVAL;
     DEVGUARD(c);
     hipStream_t s = (hipStream_t)stream;
-    const size_t ws = rx_ddos_ws_bytes(n, false);
-    if (ws > c->d_ddos_ws_cap) {
-        int rc = ensure_dev_async(&c->d_ddos_ws, &c->d_ddos_ws_cap, ws, s);
-        if (rc) return rc;
-    }
+    RCCHK(ws_grow(c->ddos.ws, rx_ddos_ws_bytes(n, false), s));
     HIPCHK(rx_ddos_window_launch(d_bits, d_len, n, thresh, d_state, d_flag, d_stat, d_summary,
-                                 c->d_ddos_ws, s));
+                                 c->ddos.ws.p, s));
     return RXG_OK;
 }
 
 // (a delivery in flight is waited for first, like every other call on the context)
 int rxg_ddos_reset(rxg_ctx *c) {
     if (!c) return RXG_EINVAL;
-    if (c->device == RXG_HOST_ONLY || !c->d_ddos_state) return RXG_OK; // (fresh at first use)
+    if (c->device == RXG_HOST_ONLY || !c->ddos.d_state) return RXG_OK; // (fresh at first use)
     DEVGUARD(c);
-    HIPCHK(hipMemsetAsync(c->d_ddos_state, 0, sizeof(rxg_ddos_state), c->stream));
+    HIPCHK(hipMemsetAsync(c->ddos.d_state, 0, sizeof(rxg_ddos_state), c->stream));
     return RXG_OK;
 }
 
-int rxg_delivery_ddos(rxg_ctx *c, const rxg_delivery *d, rxg_ddos_summary *summary) {
-    if (!c || !d || !summary) return RXG_EINVAL;
-    memset(summary, 0, sizeof(*summary));
-    if (d->set < 1 || d->set > RXG_DELIVER_DEPTH) return RXG_EINVAL;
-    const rxg_ctx::delivery_set &ds = c->dls[d->set - 1];
-    if (ds.on) return RXG_EINVAL; // (not waited for yet)
-    if (ds.ddos) *summary = *ds.h_ddos;
+static int ddos_reserve(rxg_ctx *c, dset &ds) {
+    rxg_ctx::ddos_pass &k = c->ddos;
+    RCCHK(both_alloc(&k.d_sum, &ds.ddos.h_sum, sizeof(rxg_ddos_summary)));
+    if (!k.d_state) { // fresh, ordered before the first burst's detector
+        RCCHK(dev_alloc(&k.d_state, sizeof(rxg_ddos_state)));
+        HIPCHK(hipMemsetAsync(k.d_state, 0, sizeof(rxg_ddos_state), c->stream));
+    }
     return RXG_OK;
 }
-
-int rxg_tcp_assemble_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off,
-                         const uint16_t *d_len, uint32_t n, uint32_t off_unit_log2,
-                         const rxg_verdict *d_v, rxg_segment *d_seg, rxg_tcp_stream *d_stream,
-                         uint8_t *d_payload, uint64_t payload_cap, uint32_t *d_totals, void *stream) {
-    if (!c) return RXG_EINVAL;
-    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
-    if (!d_totals || !d_payload) return RXG_EINVAL;
-    if (n && (!d_pkts || !d_off || !d_len || !d_v || !d_seg || !d_stream)) return RXG_EINVAL;
-    if (off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
-    DEVGUARD(c);
-    const int rc = k4_ws_grow(c, rx_assemble_ws_bytes(n), (hipStream_t)stream);
-    if (rc) return rc;
-    HIPCHK(rx_assemble_launch(d_pkts, d_off, d_len, n, off_unit_log2, reinterpret_cast<const uint4 *>(d_v),
-                              c->fs.tcp.id_space(), d_seg, d_stream, d_payload, payload_cap, d_totals,
-                              c->d_ss_ws, (hipStream_t)stream));
+// The detector reads the staged frames once more; bursts follow each other on
+// the stream, so the window follows submit order.  Only its summary goes back,
+// at once behind the launch (K6 has no copy_out step of its own).
+static int ddos_enqueue(rxg_ctx *c, dset &ds, const burst_view &b) {
+    rxg_ctx::ddos_pass &k = c->ddos;
+    RCCHK(ddos_launch(c, b, (uint32_t)(b.span / b.n), k.thresh, k.d_state, nullptr, nullptr, nullptr,
+                      k.d_sum, c->stream));
+    HIPCHK(copy_back(c, ds.ddos.h_sum, k.d_sum, sizeof(rxg_ddos_summary)));
     return RXG_OK;
 }
-
-int rxg_delivery_streams(rxg_ctx *c, const rxg_delivery *d, const rxg_tcp_stream **stream,
-                         uint32_t *nstream) {
-    if (!c || !d || !stream || !nstream) return RXG_EINVAL;
-    *stream = nullptr;
-    *nstream = 0;
-    if (d->set < 1 || d->set > RXG_DELIVER_DEPTH) return RXG_EINVAL;
-    const rxg_ctx::delivery_set &ds = c->dls[d->set - 1];
-    if (ds.on) return RXG_EINVAL; // (not waited for yet)
-    if (ds.assemble && ds.nstream) *stream = ds.h_ss_stream, *nstream = ds.nstream;
-    return RXG_OK;
+static void ddos_release(rxg_ctx *c) {
+    dev_free({c->ddos.ws.p, c->ddos.d_state, c->ddos.d_sum});
+    for (dset &ds : c->dls) pin_free({ds.ddos.h_sum});
 }
 
-// K7's three launches on s; the context's workspace is grown first.  An empty
-// call (no frame, or no listener id) zeroes its outputs without a launch.
-static int syncookie_impl(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off, const uint16_t *d_len,
-                          uint32_t n, uint32_t off_unit_log2, const uint4 *d_v, const uint32_t *d_lmask,
-                          uint32_t id_space, const rxg_ck_params *p, uint8_t *d_status, rxg_txd *d_txd,
-                          uint32_t *d_totals, hipStream_t s) {
-    if (n == 0 || id_space == 0) {
+// ---- SYN cookies (K7) --------------------------------------------------------
+// K7's three launches on s.  An empty call (no frame, or no listener id)
+// zeroes its outputs without a launch.
+static int ck_launch(rxg_ctx *c, const burst_view &b, const uint32_t *d_lmask, uint32_t id_space,
+                     const rxg_ck_params *p, uint8_t *d_status, rxg_txd *d_txd, uint32_t *d_totals,
+                     hipStream_t s) {
+    if (b.n == 0 || id_space == 0) {
         HIPCHK(hipMemsetAsync(d_totals, 0, 4 * sizeof(uint32_t), s));
-        if (n) HIPCHK(hipMemsetAsync(d_status, 0, n, s));
+        if (b.n) HIPCHK(hipMemsetAsync(d_status, 0, b.n, s));
         return RXG_OK;
     }
-    const size_t ws = rx_syncookie_ws_bytes(n);
-    if (ws > c->d_ck_ws_cap) { // (its uses are ordered by the caller: freed and grown in stream order)
-        int rc = ensure_dev_async(&c->d_ck_ws, &c->d_ck_ws_cap, ws, s);
-        if (rc) return rc;
-    }
-    HIPCHK(rx_syncookie_launch(d_pkts, d_off, d_len, n, off_unit_log2, d_v, d_lmask, id_space, p,
-                               d_status, d_txd, d_totals, c->d_ck_ws, s));
+    RCCHK(ws_grow(c->ck.ws, rx_syncookie_ws_bytes(b.n), s));
+    HIPCHK(rx_syncookie_launch(b.d_pkts, b.d_off, b.d_len, b.n, b.ul, b.d_out, d_lmask, id_space, p,
+                               d_status, d_txd, d_totals, c->ck.ws.p, s));
     return RXG_OK;
 }
 
@@ -2082,11 +2160,10 @@ int rxg_syncookie_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off, 
     if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
     if (n && (!d_pkts || !d_off || !d_len || !d_v || !d_status || !d_txd)) return RXG_EINVAL;
     if ((id_space && !d_lmask) || ((uintptr_t)d_txd & 15u)) return RXG_EINVAL;
-    if (off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
+    if (bad_unit(off_unit_log2)) return RXG_EINVAL;
     DEVGUARD(c);
-    return syncookie_impl(c, d_pkts, d_off, d_len, n, off_unit_log2,
-                          reinterpret_cast<const uint4 *>(d_v), d_lmask, id_space, p, d_status, d_txd,
-                          d_totals, (hipStream_t)stream);
+    return ck_launch(c, view_of(d_pkts, d_off, d_len, n, off_unit_log2, d_v), d_lmask, id_space, p,
+                     d_status, d_txd, d_totals, (hipStream_t)stream);
 }
 
 // the parameters, and the listeners as a bit mask on the device: uploaded on
@@ -2098,71 +2175,79 @@ int rxg_syncookie_set(rxg_ctx *c, const rxg_ck_params *p, const uint32_t *listen
         if (listener_ids[k] == RXG_FLOW_NONE) return RXG_EINVAL;
         if (listener_ids[k] >= space) space = listener_ids[k] + 1u;
     }
+    rxg_ctx::cookie_pass &k7 = c->ck;
     if (c->device == RXG_HOST_ONLY) {
-        c->ck_p = *p;
-        c->ck_id_space = space;
+        k7.p = *p;
+        k7.id_space = space;
         return RXG_OK;
     }
     DEVGUARD(c);
-    if (!c->ev_ck) HIPCHK(hipEventCreateWithFlags(&c->ev_ck, hipEventDisableTiming));
-    else HIPCHK(hipEventSynchronize(c->ev_ck)); // (the last upload has read ck_hmask)
+    if (!k7.ev) HIPCHK(hipEventCreateWithFlags(&k7.ev, hipEventDisableTiming));
+    else HIPCHK(hipEventSynchronize(k7.ev)); // (the last upload has read hmask)
     const size_t words = ((size_t)space + 31) / 32;
-    c->ck_hmask.assign(words, 0u);
-    for (uint32_t k = 0; k < nl; ++k) c->ck_hmask[listener_ids[k] >> 5] |= 1u << (listener_ids[k] & 31u);
+    k7.hmask.assign(words, 0u);
+    for (uint32_t k = 0; k < nl; ++k) k7.hmask[listener_ids[k] >> 5] |= 1u << (listener_ids[k] & 31u);
     if (words) {
-        int rc = ensure_dev_async(&c->d_ck_mask, &c->d_ck_mask_cap, words * sizeof(uint32_t), c->stream);
-        if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(c->d_ck_mask, c->ck_hmask.data(), words * sizeof(uint32_t),
-                              hipMemcpyHostToDevice, c->stream));
+        RCCHK(ensure_dev_async(&k7.mask.p, &k7.mask.cap, words * sizeof(uint32_t), c->stream));
+        HIPCHK(hipMemcpyAsync(k7.mask.p, k7.hmask.data(), words * sizeof(uint32_t), hipMemcpyHostToDevice,
+                              c->stream));
     }
-    HIPCHK(hipEventRecord(c->ev_ck, c->stream));
-    c->ck_p = *p;
-    c->ck_id_space = space;
+    HIPCHK(hipEventRecord(k7.ev, c->stream));
+    k7.p = *p;
+    k7.id_space = space;
     return RXG_OK;
 }
 
 int rxg_syncookie_tick(rxg_ctx *c, uint32_t t) {
     if (!c) return RXG_EINVAL;
-    c->ck_p.t = t;
+    c->ck.p.t = t;
     return RXG_OK;
 }
 
-int rxg_delivery_cookies(rxg_ctx *c, const rxg_delivery *d, const uint8_t **status,
-                         const rxg_txd **txd, uint32_t *ntxd, uint32_t totals[4]) {
-    if (!c || !d || !status || !txd || !ntxd || !totals) return RXG_EINVAL;
-    *status = nullptr, *txd = nullptr, *ntxd = 0;
-    memset(totals, 0, 4 * sizeof(uint32_t));
-    if (d->set < 1 || d->set > RXG_DELIVER_DEPTH) return RXG_EINVAL;
-    const rxg_ctx::delivery_set &ds = c->dls[d->set - 1];
-    if (ds.on) return RXG_EINVAL; // (not waited for yet)
-    if (!ds.cookie) return RXG_OK;
-    *status = ds.h_ck_status;
-    *txd = ds.h_ck_txd;
-    *ntxd = ds.h_ck_totals[0];
-    memcpy(totals, ds.h_ck_totals, 4 * sizeof(uint32_t));
+static int ck_reserve(rxg_ctx *c, dset &ds) {
+    rxg_ctx::cookie_pass &k = c->ck;
+    RCCHK(both_alloc(&k.d_status, &ds.ck.h_status, c->max_pkts));
+    RCCHK(both_alloc(&k.d_txd, &ds.ck.h_txd, (size_t)c->max_pkts * sizeof(rxg_txd)));
+    return both_alloc(&k.d_totals, &ds.ck.h_totals, 4 * sizeof(uint32_t));
+}
+// K7 reads the verdicts and the candidates' heads
+static int ck_enqueue(rxg_ctx *c, const burst_view &b) {
+    rxg_ctx::cookie_pass &k = c->ck;
+    return ck_launch(c, b, (const uint32_t *)k.mask.p, k.id_space, &k.p, k.d_status, k.d_txd, k.d_totals,
+                     c->stream);
+}
+// its status bytes, an upper-bound copy of n descriptors and its totals
+static int ck_copy_out(rxg_ctx *c, dset &ds, const burst_view &b) {
+    const rxg_ctx::cookie_pass &k = c->ck;
+    HIPCHK(copy_back(c, ds.ck.h_totals, k.d_totals, 4 * sizeof(uint32_t)));
+    HIPCHK(copy_back(c, ds.ck.h_status, k.d_status, b.n));
+    if (k.id_space) // (no listener id: no descriptor)
+        HIPCHK(copy_back(c, ds.ck.h_txd, k.d_txd, (size_t)b.n * sizeof(rxg_txd)));
     return RXG_OK;
 }
+static void ck_release(rxg_ctx *c) {
+    rxg_ctx::cookie_pass &k = c->ck;
+    dev_free({k.ws.p, k.mask.p, k.d_status, k.d_txd, k.d_totals});
+    if (k.ev) (void)hipEventDestroy(k.ev);
+    for (dset &ds : c->dls) pin_free({ds.ck.h_status, ds.ck.h_txd, ds.ck.h_totals});
+}
 
-// K8's launches on s; the context's workspace is grown first.  An empty call
-// zeroes the totals without a launch.
-static int l2_impl(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off, const uint16_t *d_len,
-                   uint32_t n, uint32_t off_unit_log2, const uint4 *d_v, const rxg_l2_params *p,
-                   uint8_t *d_status, uint8_t *d_out, uint64_t cap_bytes, uint32_t *d_roff,
-                   uint16_t *d_rlen, uint32_t *d_rsrc, uint32_t *d_totals, hipStream_t s) {
-    if (n == 0) {
+// ---- the L2 responder (K8) ---------------------------------------------------
+// K8's launches on s.  An empty call zeroes the totals without a launch.
+static int l2_launch(rxg_ctx *c, const burst_view &b, const rxg_l2_params *p, uint8_t *d_status,
+                     uint8_t *d_out, uint64_t cap_bytes, uint32_t *d_roff, uint16_t *d_rlen,
+                     uint32_t *d_rsrc, uint32_t *d_totals, hipStream_t s) {
+    if (b.n == 0) {
         HIPCHK(hipMemsetAsync(d_totals, 0, 6 * sizeof(uint32_t), s));
         return RXG_OK;
     }
-    const size_t ws = rx_l2_ws_bytes(n);
-    if (ws > c->d_l2_ws_cap) { // (its uses are ordered by the caller: freed and grown in stream order)
-        int rc = ensure_dev_async(&c->d_l2_ws, &c->d_l2_ws_cap, ws, s);
-        if (rc) return rc;
-        // (a fresh workspace: its control words start at zero; every call
-        // leaves them so)
-        HIPCHK(hipMemsetAsync(c->d_l2_ws, 0, rx_l2_ws_ctl_bytes(), s));
-    }
-    HIPCHK(rx_l2_launch(d_pkts, d_off, d_len, n, off_unit_log2, d_v, p, d_status, d_out, cap_bytes,
-                        d_roff, d_rlen, d_rsrc, d_totals, c->d_l2_ws, s));
+    rxg_ctx::l2_pass &k = c->l2;
+    bool fresh;
+    RCCHK(ws_grow(k.ws, rx_l2_ws_bytes(b.n), s, &fresh));
+    // (a fresh workspace: its control words start at zero; every call leaves them so)
+    if (fresh) HIPCHK(hipMemsetAsync(k.ws.p, 0, rx_l2_ws_ctl_bytes(), s));
+    HIPCHK(rx_l2_launch(b.d_pkts, b.d_off, b.d_len, b.n, b.ul, b.d_out, p, d_status, d_out, cap_bytes,
+                        d_roff, d_rlen, d_rsrc, d_totals, k.ws.p, s));
     return RXG_OK;
 }
 
@@ -2177,19 +2262,131 @@ int rxg_l2_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off, const u
     if (((uintptr_t)d_out & 63u) || ((uintptr_t)d_roff & 3u) || ((uintptr_t)d_rsrc & 3u) ||
         ((uintptr_t)d_rlen & 1u))
         return RXG_EINVAL;
-    if (off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
+    if (bad_unit(off_unit_log2)) return RXG_EINVAL;
     DEVGUARD(c);
-    return l2_impl(c, d_pkts, d_off, d_len, n, off_unit_log2, reinterpret_cast<const uint4 *>(d_v), p,
-                   d_status, d_out, cap_bytes, d_roff, d_rlen, d_rsrc, d_totals, (hipStream_t)stream);
+    return l2_launch(c, view_of(d_pkts, d_off, d_len, n, off_unit_log2, d_v), p, d_status, d_out,
+                     cap_bytes, d_roff, d_rlen, d_rsrc, d_totals, (hipStream_t)stream);
 }
 
 // the parameters are read at the next submit (by value into the launches); the
-// answer buffers follow cap_bytes there
+// answer buffers follow cap_bytes there (l2_reserve)
 int rxg_l2_set(rxg_ctx *c, const rxg_l2_params *p, uint64_t cap_bytes) {
     if (!c || !p || p->nlocal > RXG_L2_MAX_LOCAL) return RXG_EINVAL;
     const uint64_t bound = c->max_bytes + 64ull * c->max_pkts;
-    c->l2_p = *p;
-    c->l2_cap = (cap_bytes < bound ? cap_bytes : bound) & ~63ull;
+    c->l2.p = *p;
+    c->l2.cap = (cap_bytes < bound ? cap_bytes : bound) & ~63ull;
+    return RXG_OK;
+}
+
+static int l2_reserve(rxg_ctx *c, dset &ds) {
+    rxg_ctx::l2_pass &k = c->l2;
+    const size_t n = c->max_pkts;
+    const uint64_t room = k.cap ? k.cap : 64u; // (never a null answer buffer)
+    RCCHK(both_alloc(&k.d_status, &ds.l2.h_status, n));
+    RCCHK(both_alloc(&k.d_roff, &ds.l2.h_roff, n * sizeof(uint32_t)));
+    RCCHK(both_alloc(&k.d_rlen, &ds.l2.h_rlen, n * sizeof(uint16_t)));
+    RCCHK(both_alloc(&k.d_rsrc, &ds.l2.h_rsrc, n * sizeof(uint32_t)));
+    RCCHK(both_alloc(&k.d_totals, &ds.l2.h_totals, 6 * sizeof(uint32_t)));
+    if (k.d_out_cap < room) { // (a larger rxg_l2_set: after the bursts that use the old one)
+        HIPCHK(hipStreamSynchronize(c->stream));
+        dev_free({k.d_out});
+        k.d_out = nullptr, k.d_out_cap = 0;
+        RCCHK(dev_alloc(&k.d_out, room));
+        k.d_out_cap = room;
+    }
+    if (ds.l2.h_out_cap < room) { // (this set has been waited for: nothing writes into it)
+        pin_free({ds.l2.h_out});
+        ds.l2.h_out = nullptr, ds.l2.h_out_cap = 0;
+        RCCHK(pin_alloc(&ds.l2.h_out, room));
+        ds.l2.h_out_cap = room;
+    }
+    return RXG_OK;
+}
+// K8 reads the verdicts and the ARP / echo frames
+static int l2_enqueue(rxg_ctx *c, const burst_view &b) {
+    rxg_ctx::l2_pass &k = c->l2;
+    return l2_launch(c, b, &k.p, k.d_status, k.d_out, k.cap, k.d_roff, k.d_rlen, k.d_rsrc, k.d_totals,
+                     c->stream);
+}
+static int l2_copy_out(rxg_ctx *c, dset &ds, const burst_view &b) {
+    const rxg_ctx::l2_pass &k = c->l2;
+    const size_t n = b.n;
+    HIPCHK(copy_back(c, ds.l2.h_totals, k.d_totals, 6 * sizeof(uint32_t)));
+    HIPCHK(copy_back(c, ds.l2.h_status, k.d_status, n));
+    if (!k.p.nlocal || !k.cap) return RXG_OK; // (no answer)
+    // upper bounds: n entries, and every answer's slot is at most its frame's
+    // length rounded up to 64 B
+    const uint64_t bound = (b.span + 64ull * n + 63u) & ~63ull;
+    HIPCHK(copy_back(c, ds.l2.h_roff, k.d_roff, n * sizeof(uint32_t)));
+    HIPCHK(copy_back(c, ds.l2.h_rlen, k.d_rlen, n * sizeof(uint16_t)));
+    HIPCHK(copy_back(c, ds.l2.h_rsrc, k.d_rsrc, n * sizeof(uint32_t)));
+    HIPCHK(copy_back(c, ds.l2.h_out, k.d_out, bound < k.cap ? bound : k.cap));
+    return RXG_OK;
+}
+static void l2_release(rxg_ctx *c) {
+    rxg_ctx::l2_pass &k = c->l2;
+    dev_free({k.ws.p, k.d_status, k.d_out, k.d_roff, k.d_rlen, k.d_rsrc, k.d_totals});
+    for (dset &ds : c->dls)
+        pin_free({ds.l2.h_status, ds.l2.h_out, ds.l2.h_roff, ds.l2.h_rlen, ds.l2.h_rsrc, ds.l2.h_totals});
+}
+
+// ---- the delivery pipeline: rxg_deliver_submit / _wait ------------------------
+// the set behind a handle once waited for (the accessors clear their outputs, then ask)
+static int waited_set(rxg_ctx *c, const rxg_delivery *d, const dset **ds) {
+    if (d->set < 1 || d->set > RXG_DELIVER_DEPTH) return RXG_EINVAL;
+    *ds = &c->dls[d->set - 1];
+    return (*ds)->on ? RXG_EINVAL : RXG_OK; // (not waited for yet)
+}
+
+int rxg_delivery_runs(rxg_ctx *c, const rxg_delivery *d, const rxg_tcp_run **run, uint32_t *nrun) {
+    if (!c || !d || !run || !nrun) return RXG_EINVAL;
+    *run = nullptr, *nrun = 0;
+    const dset *ds;
+    RCCHK(waited_set(c, d, &ds));
+    if (ds->tcp.nrun) *run = ds->tcp.h_run, *nrun = ds->tcp.nrun; // (0 unless a coalescing form ran)
+    return RXG_OK;
+}
+
+int rxg_delivery_moved(rxg_ctx *c, const rxg_delivery *d, uint32_t *moved) {
+    if (!c || !d || !moved) return RXG_EINVAL;
+    *moved = 0;
+    const dset *ds;
+    RCCHK(waited_set(c, d, &ds));
+    *moved = ds->tcp.moved; // (0 unless an ordering form ran)
+    return RXG_OK;
+}
+
+int rxg_delivery_streams(rxg_ctx *c, const rxg_delivery *d, const rxg_tcp_stream **stream,
+                         uint32_t *nstream) {
+    if (!c || !d || !stream || !nstream) return RXG_EINVAL;
+    *stream = nullptr, *nstream = 0;
+    const dset *ds;
+    RCCHK(waited_set(c, d, &ds));
+    if (ds->tcp.nstream) *stream = ds->tcp.h_stream, *nstream = ds->tcp.nstream; // (0 unless assembled)
+    return RXG_OK;
+}
+
+int rxg_delivery_ddos(rxg_ctx *c, const rxg_delivery *d, rxg_ddos_summary *summary) {
+    if (!c || !d || !summary) return RXG_EINVAL;
+    memset(summary, 0, sizeof(*summary));
+    const dset *ds;
+    RCCHK(waited_set(c, d, &ds));
+    if (ds->ddos.ran) *summary = *ds->ddos.h_sum;
+    return RXG_OK;
+}
+
+int rxg_delivery_cookies(rxg_ctx *c, const rxg_delivery *d, const uint8_t **status,
+                         const rxg_txd **txd, uint32_t *ntxd, uint32_t totals[4]) {
+    if (!c || !d || !status || !txd || !ntxd || !totals) return RXG_EINVAL;
+    *status = nullptr, *txd = nullptr, *ntxd = 0;
+    memset(totals, 0, 4 * sizeof(uint32_t));
+    const dset *ds;
+    RCCHK(waited_set(c, d, &ds));
+    if (!ds->ck.ran) return RXG_OK;
+    *status = ds->ck.h_status;
+    *txd = ds->ck.h_txd;
+    *ntxd = ds->ck.h_totals[0];
+    memcpy(totals, ds->ck.h_totals, 4 * sizeof(uint32_t));
     return RXG_OK;
 }
 
@@ -2199,35 +2396,13 @@ int rxg_delivery_l2(rxg_ctx *c, const rxg_delivery *d, const uint8_t **status, c
     if (!c || !d || !status || !frames || !roff || !rlen || !rsrc || !nans || !totals) return RXG_EINVAL;
     *status = nullptr, *frames = nullptr, *roff = nullptr, *rlen = nullptr, *rsrc = nullptr, *nans = 0;
     memset(totals, 0, 6 * sizeof(uint32_t));
-    if (d->set < 1 || d->set > RXG_DELIVER_DEPTH) return RXG_EINVAL;
-    const rxg_ctx::delivery_set &ds = c->dls[d->set - 1];
-    if (ds.on) return RXG_EINVAL; // (not waited for yet)
-    if (!ds.l2) return RXG_OK;
-    *status = ds.h_l2_status, *frames = ds.h_l2_out;
-    *roff = ds.h_l2_roff, *rlen = ds.h_l2_rlen, *rsrc = ds.h_l2_rsrc;
-    *nans = ds.h_l2_totals[4];
-    memcpy(totals, ds.h_l2_totals, 6 * sizeof(uint32_t));
-    return RXG_OK;
-}
-
-int rxg_delivery_moved(rxg_ctx *c, const rxg_delivery *d, uint32_t *moved) {
-    if (!c || !d || !moved) return RXG_EINVAL;
-    *moved = 0;
-    if (d->set < 1 || d->set > RXG_DELIVER_DEPTH) return RXG_EINVAL;
-    const rxg_ctx::delivery_set &ds = c->dls[d->set - 1];
-    if (ds.on) return RXG_EINVAL; // (not waited for yet)
-    if (ds.order) *moved = ds.moved;
-    return RXG_OK;
-}
-
-int rxg_delivery_runs(rxg_ctx *c, const rxg_delivery *d, const rxg_tcp_run **run, uint32_t *nrun) {
-    if (!c || !d || !run || !nrun) return RXG_EINVAL;
-    *run = nullptr;
-    *nrun = 0;
-    if (d->set < 1 || d->set > RXG_DELIVER_DEPTH) return RXG_EINVAL;
-    const rxg_ctx::delivery_set &ds = c->dls[d->set - 1];
-    if (ds.on) return RXG_EINVAL; // (not waited for yet)
-    if (ds.gro && ds.nrun) *run = ds.h_ss_run, *nrun = ds.nrun;
+    const dset *ds;
+    RCCHK(waited_set(c, d, &ds));
+    if (!ds->l2.ran) return RXG_OK;
+    *status = ds->l2.h_status, *frames = ds->l2.h_out;
+    *roff = ds->l2.h_roff, *rlen = ds->l2.h_rlen, *rsrc = ds->l2.h_rsrc;
+    *nans = ds->l2.h_totals[4];
+    memcpy(totals, ds->l2.h_totals, 6 * sizeof(uint32_t));
     return RXG_OK;
 }
 
@@ -2235,6 +2410,73 @@ static double now_ms() {
     struct timespec ts;
     clock_gettime(CLOCK_MONOTONIC, &ts);
     return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
+}
+
+// which passes a delivery burst runs: the context's flags and tables at submit
+struct delivery_plan {
+    uint32_t nf;         // the UDP id space
+    bool udp, tcp;       // K3 (1 .. RXG_COMPACT_MAX_FLOWS UDP ids), K4 (any TCP id)
+    k4_form form;
+    bool ddos, ck, l2;
+    uint8_t *h_payload;  // where the TCP payloads go (deliver_pick_payload)
+};
+static delivery_plan plan_of(const rxg_ctx *c) {
+    const uint32_t fl = c->deliver_flags, nf = c->fs.udp.id_space();
+    return {nf, nf > 0 && nf <= RXG_COMPACT_MAX_FLOWS, c->fs.tcp.id_space() > 0, k4_form::of(fl),
+            (fl & RXG_DLV_DDOS) != 0, (fl & RXG_DLV_SYNCOOKIE) != 0, (fl & RXG_DLV_L2) != 0, nullptr};
+}
+
+// The TCP payloads of this burst: a free pooled buffer (a hold the caller can
+// take, rxg_payload_hold), else the set's own one (valid until the set is
+// reused: tcp_payload_ref = -1).  The library's hold on the buffer of this
+// set's previous burst ends here.  In place (RXG_DLV_TCP_IN_PLACE): no payload
+// is gathered or copied back; the payloads stay in the caller's frames.
+static int deliver_pick_payload(rxg_ctx *c, dset &ds, bool inplace, uint8_t **h_payload) {
+    if (ds.pl >= 0) c->pl[ds.pl].refs.fetch_sub(1, std::memory_order_acq_rel);
+    ds.pl = -1;
+    *h_payload = nullptr;
+    if (inplace) return RXG_OK;
+    for (int k = 0; k < RXG_PAYLOAD_BUFS && ds.pl < 0; ++k) {
+        rxg_ctx::pl_buf &b = c->pl[k];
+        if (b.refs.load(std::memory_order_acquire) != 0) continue;
+        if (!b.h && hipHostMalloc((void **)&b.h, c->max_bytes, 0) != hipSuccess) {
+            b.h = nullptr; // (out of pinned memory: the set's own buffer)
+            (void)hipGetLastError();
+            break;
+        }
+        b.refs.store(1, std::memory_order_release);
+        ds.pl = k;
+    }
+    if (ds.pl < 0) RCCHK(pin_alloc(&ds.tcp.h_payload, c->max_bytes));
+    *h_payload = ds.pl >= 0 ? c->pl[ds.pl].h : ds.tcp.h_payload;
+    return RXG_OK;
+}
+
+// Every device step and copy of the burst.  Every result goes back in one
+// round trip: the counts with upper-bound copies of the records (n of each) and
+// payloads (the staged span bounds the sum of the 16-B padded payloads), so no
+// synchronisation sits between the passes and their copy out.  The next set's
+// passes reuse the device buffers after these copies, in stream order.
+static int deliver_enqueue(rxg_ctx *c, dset &ds, const delivery_plan &p, rxg_ctx::slot &sl,
+                           const staged &st, uint32_t n, rxg_verdict *out, uint64_t t) {
+    const burst_view b = slot_view(sl, st, n);
+    HIPCHK(hipEventRecord(ds.tev[0], c->s_h2d));
+    RCCHK(submit_slot(c, sl, st.src, st.span, sl.h_off, sl.h_len, n, st.ul, out, t, st.pulled));
+    HIPCHK(hipEventRecord(ds.tev[1], c->s_h2d));  // after the copy in
+    HIPCHK(hipEventRecord(ds.tev[2], c->stream)); // after K1
+    // the passes follow the classify on the context's stream
+    if (p.udp) RCCHK(udp_enqueue(c, b));
+    if (p.tcp) RCCHK(tcp_enqueue(c, p.form, b));
+    if (p.ddos) RCCHK(ddos_enqueue(c, ds, b));
+    if (p.ck) RCCHK(ck_enqueue(c, b));
+    if (p.l2) RCCHK(l2_enqueue(c, b));
+    HIPCHK(hipEventRecord(ds.tev[3], c->stream)); // after the passes
+    if (p.udp) RCCHK(udp_copy_out(c, ds, b, p.nf));
+    if (p.tcp) RCCHK(tcp_copy_out(c, ds, p.form, b, p.h_payload));
+    if (p.ck) RCCHK(ck_copy_out(c, ds, b));
+    if (p.l2) RCCHK(l2_copy_out(c, ds, b));
+    HIPCHK(hipEventRecord(ds.tev[4], c->stream)); // after the results' copy out
+    return RXG_OK;
 }
 
 int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *out,
@@ -2246,296 +2488,56 @@ int rxg_deliver_submit(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_verdict *
     if (n > c->max_pkts || !c->slots[0].h_stage) return RXG_ERANGE;
     // the next set in turn, which must have been waited for
     const uint32_t si = c->dl_next;
-    rxg_ctx::delivery_set &ds = c->dls[si];
+    dset &ds = c->dls[si];
     if (ds.on) return RXG_EINVAL; // (RXG_DELIVER_DEPTH bursts in flight already)
-    const uint32_t nf = c->fs.udp.id_space();
-    const bool udp = nf > 0 && nf <= RXG_COMPACT_MAX_FLOWS;
+    delivery_plan p = plan_of(c);
     DEVGUARD(c);
-    const double t0 = now_ms();
-    // results buffers, first use (each set last-allocated-first-checked: a
-    // failed allocation leaves the rest for the next call to retry)
-    if (udp && !ds.h_cp_totals) {
-        if (!c->d_cp_dg) HIPCHK(hipMalloc(&c->d_cp_dg, (size_t)c->max_pkts * sizeof(rxg_dgram)));
-        if (!c->d_cp_first)
-            HIPCHK(hipMalloc(&c->d_cp_first, (RXG_COMPACT_MAX_FLOWS + 1) * sizeof(uint32_t)));
-        if (!c->d_cp_payload) HIPCHK(hipMalloc(&c->d_cp_payload, c->max_bytes));
-        if (!c->d_cp_totals) HIPCHK(hipMalloc(&c->d_cp_totals, 4 * sizeof(uint32_t)));
-        if (!ds.h_cp_dg)
-            HIPCHK(hipHostMalloc((void **)&ds.h_cp_dg, (size_t)c->max_pkts * sizeof(rxg_dgram), 0));
-        if (!ds.h_cp_first)
-            HIPCHK(hipHostMalloc((void **)&ds.h_cp_first, (RXG_COMPACT_MAX_FLOWS + 1) * sizeof(uint32_t), 0));
-        if (!ds.h_cp_payload) HIPCHK(hipHostMalloc((void **)&ds.h_cp_payload, c->max_bytes, 0));
-        HIPCHK(hipHostMalloc((void **)&ds.h_cp_totals, 4 * sizeof(uint32_t), 0));
-    }
-    if (!ds.h_ss_totals) {
-        if (!c->d_ss_seg) HIPCHK(hipMalloc(&c->d_ss_seg, (size_t)c->max_pkts * sizeof(rxg_segment)));
-        if (!c->d_ss_payload) HIPCHK(hipMalloc(&c->d_ss_payload, c->max_bytes));
-        if (!c->d_ss_totals) HIPCHK(hipMalloc(&c->d_ss_totals, 6 * sizeof(uint32_t)));
-        if (!ds.h_ss_seg)
-            HIPCHK(hipHostMalloc((void **)&ds.h_ss_seg, (size_t)c->max_pkts * sizeof(rxg_segment), 0));
-        HIPCHK(hipHostMalloc((void **)&ds.h_ss_totals, 6 * sizeof(uint32_t), 0));
-    }
-    const bool gro = (c->deliver_flags & RXG_DLV_TCP_GRO) != 0;
-    const bool assemble = (c->deliver_flags & RXG_DLV_TCP_ASSEMBLE) != 0;
-    // (assembly runs the ordering stage itself and reports its moved count)
-    const bool order = (c->deliver_flags & RXG_DLV_TCP_ORDER) != 0 || assemble;
-    if (assemble) {
-        if (!c->d_ss_stream)
-            HIPCHK(hipMalloc(&c->d_ss_stream, (size_t)c->max_pkts * sizeof(rxg_tcp_stream)));
-        if (!ds.h_ss_stream)
-            HIPCHK(hipHostMalloc((void **)&ds.h_ss_stream,
-                                 (size_t)c->max_pkts * sizeof(rxg_tcp_stream), 0));
-    }
-    if (gro) {
-        if (!c->d_ss_run) HIPCHK(hipMalloc(&c->d_ss_run, (size_t)c->max_pkts * sizeof(rxg_tcp_run)));
-        if (!ds.h_ss_run)
-            HIPCHK(hipHostMalloc((void **)&ds.h_ss_run, (size_t)c->max_pkts * sizeof(rxg_tcp_run), 0));
-    }
-    const bool ddos = (c->deliver_flags & RXG_DLV_DDOS) != 0;
-    if (ddos) {
-        if (!c->d_ddos_sum) HIPCHK(hipMalloc(&c->d_ddos_sum, sizeof(rxg_ddos_summary)));
-        if (!ds.h_ddos) HIPCHK(hipHostMalloc((void **)&ds.h_ddos, sizeof(rxg_ddos_summary), 0));
-        if (!c->d_ddos_state) { // fresh, ordered before the first burst's detector
-            HIPCHK(hipMalloc(&c->d_ddos_state, sizeof(rxg_ddos_state)));
-            HIPCHK(hipMemsetAsync(c->d_ddos_state, 0, sizeof(rxg_ddos_state), c->stream));
-        }
-    }
-    const bool cookie = (c->deliver_flags & RXG_DLV_SYNCOOKIE) != 0;
-    if (cookie) {
-        if (!c->d_ck_status) HIPCHK(hipMalloc(&c->d_ck_status, c->max_pkts));
-        if (!c->d_ck_txd) HIPCHK(hipMalloc(&c->d_ck_txd, (size_t)c->max_pkts * sizeof(rxg_txd)));
-        if (!c->d_ck_totals) HIPCHK(hipMalloc(&c->d_ck_totals, 4 * sizeof(uint32_t)));
-        if (!ds.h_ck_status) HIPCHK(hipHostMalloc((void **)&ds.h_ck_status, c->max_pkts, 0));
-        if (!ds.h_ck_txd)
-            HIPCHK(hipHostMalloc((void **)&ds.h_ck_txd, (size_t)c->max_pkts * sizeof(rxg_txd), 0));
-        if (!ds.h_ck_totals) HIPCHK(hipHostMalloc((void **)&ds.h_ck_totals, 4 * sizeof(uint32_t), 0));
-    }
-    const bool l2 = (c->deliver_flags & RXG_DLV_L2) != 0;
-    const uint64_t l2_room = c->l2_cap ? c->l2_cap : 64u; // (never a null answer buffer)
-    if (l2) {
-        if (!c->d_l2_status) HIPCHK(hipMalloc(&c->d_l2_status, c->max_pkts));
-        if (!c->d_l2_roff) HIPCHK(hipMalloc(&c->d_l2_roff, (size_t)c->max_pkts * sizeof(uint32_t)));
-        if (!c->d_l2_rlen) HIPCHK(hipMalloc(&c->d_l2_rlen, (size_t)c->max_pkts * sizeof(uint16_t)));
-        if (!c->d_l2_rsrc) HIPCHK(hipMalloc(&c->d_l2_rsrc, (size_t)c->max_pkts * sizeof(uint32_t)));
-        if (!c->d_l2_totals) HIPCHK(hipMalloc(&c->d_l2_totals, 6 * sizeof(uint32_t)));
-        if (c->d_l2_out_cap < l2_room) { // (a larger rxg_l2_set: after the bursts that use the old one)
-            HIPCHK(hipStreamSynchronize(c->stream));
-            (void)hipFree(c->d_l2_out);
-            c->d_l2_out = nullptr, c->d_l2_out_cap = 0;
-            HIPCHK(hipMalloc(&c->d_l2_out, l2_room));
-            c->d_l2_out_cap = l2_room;
-        }
-        if (!ds.h_l2_status) HIPCHK(hipHostMalloc((void **)&ds.h_l2_status, c->max_pkts, 0));
-        if (!ds.h_l2_roff)
-            HIPCHK(hipHostMalloc((void **)&ds.h_l2_roff, (size_t)c->max_pkts * sizeof(uint32_t), 0));
-        if (!ds.h_l2_rlen)
-            HIPCHK(hipHostMalloc((void **)&ds.h_l2_rlen, (size_t)c->max_pkts * sizeof(uint16_t), 0));
-        if (!ds.h_l2_rsrc)
-            HIPCHK(hipHostMalloc((void **)&ds.h_l2_rsrc, (size_t)c->max_pkts * sizeof(uint32_t), 0));
-        if (!ds.h_l2_totals) HIPCHK(hipHostMalloc((void **)&ds.h_l2_totals, 6 * sizeof(uint32_t), 0));
-        if (ds.h_l2_out_cap < l2_room) { // (this set has been waited for: nothing writes into it)
-            if (ds.h_l2_out) (void)hipHostFree(ds.h_l2_out);
-            ds.h_l2_out = nullptr, ds.h_l2_out_cap = 0;
-            HIPCHK(hipHostMalloc((void **)&ds.h_l2_out, l2_room, 0));
-            ds.h_l2_out_cap = l2_room;
-        }
-    }
+    ds.t0 = now_ms(); // (the set is idle: its times are read only while it is on)
+    // the buffers of every pass of the plan (first use, or a larger rxg_l2_set), the phase events
+    if (p.udp) RCCHK(udp_reserve(c, ds.udp));
+    RCCHK(tcp_reserve(c, ds, p.form));
+    if (p.ddos) RCCHK(ddos_reserve(c, ds));
+    if (p.ck) RCCHK(ck_reserve(c, ds));
+    if (p.l2) RCCHK(l2_reserve(c, ds));
     for (hipEvent_t &e : ds.tev)
         if (!e) HIPCHK(hipEventCreate(&e));
-    // the TCP payloads of this burst: a free pooled buffer (a hold the caller
-    // can take, rxg_payload_hold), else the set's own one (valid until the
-    // set is reused: tcp_payload_ref = -1).  The library's hold on the
-    // buffer of this set's previous burst ends here.  In place
-    // (RXG_DLV_TCP_IN_PLACE): no payload is gathered or copied back; the
-    // payloads stay in the caller's frames.
-    const bool inplace = (c->deliver_flags & RXG_DLV_TCP_IN_PLACE) != 0;
-    if (ds.pl >= 0) c->pl[ds.pl].refs.fetch_sub(1, std::memory_order_acq_rel);
-    ds.pl = -1;
-    for (int k = 0; k < RXG_PAYLOAD_BUFS && ds.pl < 0 && !inplace; ++k) {
-        rxg_ctx::pl_buf &b = c->pl[k];
-        if (b.refs.load(std::memory_order_acquire) != 0) continue;
-        if (!b.h && hipHostMalloc((void **)&b.h, c->max_bytes, 0) != hipSuccess) {
-            b.h = nullptr; // (out of pinned memory: the set's own buffer)
-            (void)hipGetLastError();
-            break;
-        }
-        b.refs.store(1, std::memory_order_release);
-        ds.pl = k;
-    }
-    if (ds.pl < 0 && !inplace && !ds.h_ss_payload)
-        HIPCHK(hipHostMalloc((void **)&ds.h_ss_payload, c->max_bytes, 0));
-    d->seg = ds.h_ss_seg;
+    RCCHK(deliver_pick_payload(c, ds, p.form.inplace, &p.h_payload));
+    d->seg = ds.tcp.h_seg;
     d->tcp_payload_ref = ds.pl;
-    d->tcp_payload = inplace ? nullptr : ds.pl >= 0 ? c->pl[ds.pl].h : ds.h_ss_payload;
+    d->tcp_payload = p.h_payload;
     d->set = si + 1;
-    if (udp) {
-        d->dgram = ds.h_cp_dg;
-        d->first = ds.h_cp_first;
-        d->udp_payload = ds.h_cp_payload;
-        memset(ds.h_cp_first, 0, (nf + 1) * sizeof(uint32_t));
+    if (p.udp) {
+        d->dgram = ds.udp.h_dg;
+        d->first = ds.udp.h_first;
+        d->udp_payload = ds.udp.h_payload;
+        memset(ds.udp.h_first, 0, (p.nf + 1) * sizeof(uint32_t));
     }
-    ds.on = ds.udp = ds.tcp = ds.gro = ds.order = ds.ddos = ds.assemble = ds.cookie = ds.l2 = false;
-    ds.nrun = ds.moved = ds.nstream = 0;
+    // the set is rotated and holds nothing yet: what ran is marked once every step is queued
+    ds.on = ds.udp.ran = ds.tcp.ran = ds.ddos.ran = ds.ck.ran = ds.l2.ran = false;
+    ds.tcp.nrun = ds.tcp.moved = ds.tcp.nstream = 0;
     ds.ticket = 0;
-    ds.t0 = t0;
     c->dl_next = (si + 1) % RXG_DELIVER_DEPTH;
     if (n == 0) return RXG_OK;
     const uint64_t t = c->next_ticket++;
     rxg_ctx::slot &sl = c->slots[t % RXG_PIPE_DEPTH];
     staged st;
-    int rc = gather_mbufs(c, sl, m, n, &st, true);
-    if (rc) return rc;
-    const uint64_t pos = st.bound;
-    const double t1 = now_ms();
-    bool tcp = false;
-    // every device step and copy of the burst; on an error after the first is
-    // queued, the streams are drained so nothing still writes into the set
-    auto enqueue = [&]() -> int {
-        HIPCHK(hipEventRecord(ds.tev[0], c->s_h2d));
-        rc = submit_slot(c, sl, st.src, st.span, sl.h_off, sl.h_len, n, st.ul, out, t, st.pulled);
-        if (rc) return rc;
-        HIPCHK(hipEventRecord(ds.tev[1], c->s_h2d)); // after the copy in
-        HIPCHK(hipEventRecord(ds.tev[2], c->stream)); // after K1
-        // the compactions follow the classify on the context's stream
-        if (udp)
-            if ((rc = compact_impl(c, sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, sl.d_out, c->d_cp_dg,
-                                   c->d_cp_first, c->d_cp_payload, c->max_bytes, c->d_cp_totals,
-                                   c->stream)))
-                return rc;
-        tcp = c->fs.tcp.id_space() > 0;
-        if (tcp) {
-            const uint32_t nt = c->fs.tcp.id_space();
-            const size_t ws = assemble ? rx_assemble_ws_bytes(n)
-                              : order  ? rx_order_ws_bytes(n)
-                              : gro    ? rx_gro_ws_bytes(n)
-                                       : rx_segsort_ws_bytes(n);
-            if ((rc = k4_ws_grow(c, ws, c->stream))) return rc;
-            if (assemble)
-                HIPCHK(rx_assemble_launch(sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, sl.d_out, nt,
-                                          c->d_ss_seg, c->d_ss_stream, c->d_ss_payload, c->max_bytes,
-                                          c->d_ss_totals, c->d_ss_ws, c->stream));
-            else if (order)
-                HIPCHK(rx_order_launch(sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, sl.d_out, nt,
-                                       gro ? c->gro_window : 0u, c->d_ss_seg, c->d_ss_run,
-                                       inplace ? nullptr : c->d_ss_payload, c->max_bytes,
-                                       c->d_ss_totals, c->d_ss_ws, c->stream));
-            else if (gro)
-                HIPCHK(rx_gro_launch(sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, sl.d_out, nt,
-                                     c->gro_window, c->d_ss_seg, c->d_ss_run, c->d_ss_payload,
-                                     c->max_bytes, c->d_ss_totals, c->d_ss_ws, c->stream));
-            else
-                HIPCHK(rx_segsort_launch(sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, sl.d_out, nt,
-                                         c->d_ss_seg, inplace ? nullptr : c->d_ss_payload, c->max_bytes,
-                                         c->d_ss_totals, c->d_ss_ws, c->stream));
-        }
-        // the flood detector (RXG_DLV_DDOS) reads the staged frames once more;
-        // bursts follow each other on the stream, so the window follows
-        // submit order.  Only its summary goes back.
-        if (ddos) {
-            if ((rc = ddos_impl(c, sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, (uint32_t)(st.span / n),
-                                c->ddos_thresh, c->d_ddos_state, nullptr, nullptr, nullptr,
-                                c->d_ddos_sum, c->stream)))
-                return rc;
-            HIPCHK(hipMemcpyAsync(ds.h_ddos, c->d_ddos_sum, sizeof(rxg_ddos_summary),
-                                  hipMemcpyDeviceToHost, c->stream));
-        }
-        // SYN cookies (RXG_DLV_SYNCOOKIE): K7 reads the verdicts and the
-        // candidates' heads; its status bytes, an upper-bound copy of n
-        // descriptors and its totals go back with the other results
-        if (cookie) {
-            if ((rc = syncookie_impl(c, sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, sl.d_out,
-                                     (const uint32_t *)c->d_ck_mask, c->ck_id_space, &c->ck_p,
-                                     c->d_ck_status, c->d_ck_txd, c->d_ck_totals, c->stream)))
-                return rc;
-        }
-        // the L2 responder (RXG_DLV_L2): K8 reads the verdicts and the ARP /
-        // echo frames; its status bytes, totals and answers go back with the
-        // other results
-        if (l2) {
-            if ((rc = l2_impl(c, sl.d_pkts, sl.d_off, sl.d_len, n, st.ul, sl.d_out, &c->l2_p,
-                              c->d_l2_status, c->d_l2_out, c->l2_cap, c->d_l2_roff, c->d_l2_rlen,
-                              c->d_l2_rsrc, c->d_l2_totals, c->stream)))
-                return rc;
-        }
-        HIPCHK(hipEventRecord(ds.tev[3], c->stream)); // after K3 / K4
-        // every result in one round trip: the counts with upper-bound copies of
-        // the records (n of each) and payloads (the staged span bounds the sum of
-        // the 16-B padded payloads), so no synchronisation sits between the
-        // compactions and their copy out.  The next set's compactions reuse the
-        // device buffers after these copies, in stream order.
-        if (udp) {
-            HIPCHK(hipMemcpyAsync(ds.h_cp_totals, c->d_cp_totals, 3 * sizeof(uint32_t),
-                                  hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(ds.h_cp_first, c->d_cp_first, (nf + 1) * sizeof(uint32_t),
-                                  hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(ds.h_cp_dg, c->d_cp_dg, (size_t)n * sizeof(rxg_dgram),
-                                  hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(ds.h_cp_payload, c->d_cp_payload, pos, hipMemcpyDeviceToHost,
-                                  c->stream));
-        }
-        if (tcp) {
-            HIPCHK(hipMemcpyAsync(ds.h_ss_totals, c->d_ss_totals,
-                                  (assemble ? 6 : order ? 5 : gro ? 4 : 3) * sizeof(uint32_t),
-                                  hipMemcpyDeviceToHost, c->stream));
-            if (assemble) // (the streams cross with the records: at most n of them)
-                HIPCHK(hipMemcpyAsync(ds.h_ss_stream, c->d_ss_stream,
-                                      (size_t)n * sizeof(rxg_tcp_stream), hipMemcpyDeviceToHost,
-                                      c->stream));
-            if (gro) // (the runs cross with the records: at most n of them)
-                HIPCHK(hipMemcpyAsync(ds.h_ss_run, c->d_ss_run, (size_t)n * sizeof(rxg_tcp_run),
-                                      hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(ds.h_ss_seg, c->d_ss_seg, (size_t)n * sizeof(rxg_segment),
-                                  hipMemcpyDeviceToHost, c->stream));
-            if (!inplace)
-                HIPCHK(hipMemcpyAsync(const_cast<uint8_t *>(d->tcp_payload), c->d_ss_payload, pos,
-                                      hipMemcpyDeviceToHost, c->stream));
-        }
-        if (cookie) {
-            HIPCHK(hipMemcpyAsync(ds.h_ck_totals, c->d_ck_totals, 4 * sizeof(uint32_t),
-                                  hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(ds.h_ck_status, c->d_ck_status, n, hipMemcpyDeviceToHost, c->stream));
-            if (c->ck_id_space) // (no listener id: no descriptor)
-                HIPCHK(hipMemcpyAsync(ds.h_ck_txd, c->d_ck_txd, (size_t)n * sizeof(rxg_txd),
-                                      hipMemcpyDeviceToHost, c->stream));
-        }
-        if (l2) {
-            HIPCHK(hipMemcpyAsync(ds.h_l2_totals, c->d_l2_totals, 6 * sizeof(uint32_t),
-                                  hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(ds.h_l2_status, c->d_l2_status, n, hipMemcpyDeviceToHost, c->stream));
-            if (c->l2_p.nlocal && c->l2_cap) { // (else no answer)
-                // upper bounds: n entries, and every answer's slot is at most
-                // its frame's length rounded up to 64 B
-                const uint64_t bound = ((uint64_t)st.span + 64ull * n + 63u) & ~63ull;
-                HIPCHK(hipMemcpyAsync(ds.h_l2_roff, c->d_l2_roff, (size_t)n * sizeof(uint32_t),
-                                      hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(hipMemcpyAsync(ds.h_l2_rlen, c->d_l2_rlen, (size_t)n * sizeof(uint16_t),
-                                      hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(hipMemcpyAsync(ds.h_l2_rsrc, c->d_l2_rsrc, (size_t)n * sizeof(uint32_t),
-                                      hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(hipMemcpyAsync(ds.h_l2_out, c->d_l2_out, bound < c->l2_cap ? bound : c->l2_cap,
-                                      hipMemcpyDeviceToHost, c->stream));
-            }
-        }
-        HIPCHK(hipEventRecord(ds.tev[4], c->stream)); // after the results' copy out
-        return RXG_OK;
-    };
-    if ((rc = enqueue())) {
+    RCCHK(gather_mbufs(c, sl, m, n, &st, true));
+    ds.t1 = now_ms();
+    const int rc = deliver_enqueue(c, ds, p, sl, st, n, out, t);
+    if (rc) { // some steps may be queued: drained, so nothing still writes into the set
         (void)hipStreamSynchronize(c->s_h2d);
         (void)hipStreamSynchronize(c->stream);
         (void)hipStreamSynchronize(c->s_d2h);
         return rc;
     }
     ds.on = true;
-    ds.udp = udp;
-    ds.tcp = tcp;
-    ds.gro = tcp && gro;
-    ds.order = tcp && order;
-    ds.assemble = tcp && assemble;
-    ds.ddos = ddos;
-    ds.cookie = cookie;
-    ds.l2 = l2;
+    ds.udp.ran = p.udp;
+    ds.tcp.ran = p.tcp;
+    ds.tcp.form = p.form;
+    ds.ddos.ran = p.ddos;
+    ds.ck.ran = p.ck;
+    ds.l2.ran = p.l2;
     ds.ticket = t;
-    ds.t1 = t1;
     return RXG_OK;
 }
 
@@ -2546,21 +2548,22 @@ int rxg_deliver_wait(rxg_ctx *c, rxg_delivery *d, float ms[8]) {
     if (ms) memset(ms, 0, 8 * sizeof(float));
     if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
     if (d->set < 1 || d->set > RXG_DELIVER_DEPTH) return RXG_EINVAL;
-    rxg_ctx::delivery_set &ds = c->dls[d->set - 1];
+    dset &ds = c->dls[d->set - 1];
     if (!ds.on) return RXG_OK; // (an empty burst, or waited for already)
     ds.on = false;
     DEVGUARD(c);
     HIPCHK(hipEventSynchronize(ds.tev[4]));
-    int rc = rxg_wait(c, ds.ticket); // (the verdicts' copy out, on s_d2h)
-    if (rc) return rc;
-    const bool udp = ds.udp, tcp = ds.tcp;
-    if ((udp && ds.h_cp_totals[2]) || (tcp && ds.h_ss_totals[2]))
+    RCCHK(rxg_wait(c, ds.ticket)); // (the verdicts' copy out, on s_d2h)
+    if ((ds.udp.ran && ds.udp.h_totals[2]) || (ds.tcp.ran && ds.tcp.h_totals[2]))
         return RXG_ERANGE; // (not reached: staging bounds the payloads)
-    if (udp) d->ndgram = ds.h_cp_totals[0], d->udp_bytes = ds.h_cp_totals[1];
-    if (tcp) d->nseg = ds.h_ss_totals[0], d->tcp_bytes = ds.h_ss_totals[1];
-    if (ds.gro) ds.nrun = ds.h_ss_totals[3];
-    if (ds.order) ds.moved = ds.h_ss_totals[4];
-    if (ds.assemble) ds.nstream = ds.h_ss_totals[3];
+    if (ds.udp.ran) d->ndgram = ds.udp.h_totals[0], d->udp_bytes = ds.udp.h_totals[1];
+    if (ds.tcp.ran) {
+        const uint32_t *tot = ds.tcp.h_totals;
+        d->nseg = tot[0], d->tcp_bytes = tot[1];
+        if (ds.tcp.form.gro) ds.tcp.nrun = tot[3];
+        if (ds.tcp.form.order) ds.tcp.moved = tot[4];
+        if (ds.tcp.form.assemble) ds.tcp.nstream = tot[3];
+    }
     if (ms) {
         ms[0] = (float)(ds.t1 - ds.t0);
         for (int k = 0; k < 4; ++k) HIPCHK(hipEventElapsedTime(&ms[k + 1], ds.tev[k], ds.tev[k + 1]));
@@ -2582,11 +2585,10 @@ int rxg_process_mbufs_deliver(rxg_ctx *c, rxg_mbuf *const *m, uint32_t n, rxg_ve
 
 int rxg_tx_cksum_dev(rxg_ctx *c, uint8_t *d_pkts, const uint32_t *d_off, const uint16_t *d_len,
                      uint32_t n, uint32_t off_unit_log2, uint32_t len_hint, void *stream) {
-    if (!c) return RXG_EINVAL;
-    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
+    RCCHK(dev_ctx(c));
     if (n == 0) return RXG_OK;
     if (!d_pkts || !d_off || !d_len) return RXG_EINVAL;
-    if (off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
+    if (bad_unit(off_unit_log2)) return RXG_EINVAL;
     DEVGUARD(c);
     HIPCHK(tx_cksum_launch(d_pkts, d_off, d_len, n, off_unit_log2, len_hint, c->tune_tx,
                            c->tune_tx_bpc, (hipStream_t)stream));
@@ -2647,7 +2649,7 @@ int rxg_rss_split_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off,
     if (!c || !d_first || n_shards == 0 || n_shards > RXG_MAX_SHARDS) return RXG_EINVAL;
     if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
     if (n && (!d_pkts || !d_off || !d_len || !d_perm)) return RXG_EINVAL;
-    if (off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
+    if (bad_unit(off_unit_log2)) return RXG_EINVAL;
     DEVGUARD(c);
     const hipStream_t s = (hipStream_t)stream;
     const size_t ws = rx_split_ws_bytes(n, n_shards);
@@ -2668,7 +2670,7 @@ int rxg_gather_dev(rxg_ctx *c, const uint8_t *d_pkts, const uint32_t *d_off,
     if (count == 0) return RXG_OK;
     if (!d_pkts || !d_off || !d_len || !d_idx || !d_dst || !d_dst_off || !d_dst_len)
         return RXG_EINVAL;
-    if (off_unit_log2 < 4 || off_unit_log2 > 16) return RXG_EINVAL;
+    if (bad_unit(off_unit_log2)) return RXG_EINVAL;
     DEVGUARD(c);
     const hipStream_t s = (hipStream_t)stream;
     const size_t ws = rx_gather_ws_bytes(count);
@@ -2693,8 +2695,7 @@ int rxg_tx_encode_dev(rxg_ctx *c, const rxg_txd *d_txd, uint32_t n, const uint8_
                       uint8_t *d_pkts, uint64_t cap_bytes, uint32_t slot_bytes, uint32_t *d_off,
                       uint16_t *d_len, uint32_t len_hint, uint32_t flags, uint32_t *d_totals,
                       void *stream) {
-    if (!c) return RXG_EINVAL;
-    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
+    RCCHK(dev_ctx(c));
     if (slot_bytes & 63u) return RXG_EINVAL;
     if (!d_totals) return RXG_EINVAL;
     if (n && (!d_txd || !d_pkts || !d_off || !d_len)) return RXG_EINVAL;
@@ -2779,8 +2780,7 @@ int rxg_tx_encode_tso_dev(rxg_ctx *c, const rxg_txd *d_txd, uint32_t n, const ui
                           uint32_t *d_off, uint16_t *d_len, uint32_t out_cap, uint32_t *d_first,
                           uint32_t *d_nseg, uint32_t len_hint, uint32_t flags, uint32_t *d_totals,
                           void *stream) {
-    if (!c) return RXG_EINVAL;
-    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
+    RCCHK(dev_ctx(c));
     if ((slot_bytes & 63u) || (mss & 3u)) return RXG_EINVAL;
     if (!d_totals) return RXG_EINVAL;
     if (n && (!d_txd || !d_pkts || !d_first || !d_nseg || (out_cap && (!d_off || !d_len))))
@@ -2909,8 +2909,7 @@ int rxg_flow_counts(rxg_ctx *c, uint64_t *counts, uint32_t ncounts) {
 }
 
 int rxg_counts_reset(rxg_ctx *c) {
-    if (!c) return RXG_EINVAL;
-    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
+    RCCHK(dev_ctx(c));
     DEVGUARD(c);
     int rc = bursts_drain(c);
     if (rc) return rc;
