@@ -51,6 +51,12 @@ hipError_t tx_encode_tso_launch(const void *txd, uint32_t n, const uint8_t *pay,
                                 uint32_t len_hint, uint32_t flags, uint32_t *totals, void *ws,
                                 uint32_t variant, uint32_t bpc_cap, hipStream_t s);
 size_t txe_tso_ws_bytes(uint32_t n, uint32_t out_cap);
+hipError_t tx_encode_frag_launch(const void *txd, uint32_t n, const uint8_t *pay, uint32_t mss,
+                                 uint32_t mtu, uint8_t *pkts, uint64_t cap, uint32_t slot,
+                                 uint32_t *off, uint16_t *len, uint32_t out_cap, uint32_t *first,
+                                 uint32_t *nseg, uint32_t len_hint, uint32_t flags, uint32_t *totals,
+                                 void *ws, uint32_t variant, uint32_t bpc_cap, hipStream_t s);
+size_t txe_frag_ws_bytes(uint32_t n, uint32_t out_cap);
 size_t rx_split_ws_bytes(uint32_t n, uint32_t nsh);
 hipError_t rx_split_launch(const uint8_t *pkts, const uint32_t *off, const uint16_t *len,
                            uint32_t n, uint32_t unit_log2, uint32_t nsh, uint32_t *first,
@@ -2856,6 +2862,107 @@ int rxg_tx_encode_tso(rxg_ctx *c, const rxg_txd *txd, uint32_t n, const uint8_t 
                                reinterpret_cast<uint32_t *>(d + o_nsg),
                                (uint32_t)(need / (ne ? ne : 1)), flags,
                                reinterpret_cast<uint32_t *>(d + o_tot), s);
+    if (rc) return rc;
+    uint32_t tot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(tot, d + o_tot, 32, hipMemcpyDeviceToHost, s));
+    if (ne) {
+        HIPCHK(hipMemcpyAsync(off, d + o_off, ne * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(len, d + o_len, ne * 2, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipMemcpyAsync(first, d + o_fst, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(nseg, d + o_nsg, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const uint64_t used = ((uint64_t)tot[2] << 32) | tot[1];
+    if (used > need) return RXG_EHIP; // (cannot happen: the kernel's own capacity rule)
+    if (used) HIPCHK(hipMemcpy(pkts, d + o_pkt, used, hipMemcpyDeviceToHost));
+    if (span) *span = used;
+    return tot[3] ? RXG_ERANGE : RXG_OK;
+}
+
+// K5 with both cuts, TCP segmentation and IPv4 fragmentation of UDP datagrams:
+// the layout pass (in d_aux, with the entry map and a partial-sum word per
+// entry), the encoder over the entries and the cut datagrams' checksums on
+// `stream`
+static inline bool txe_mtu_ok(uint32_t mtu) { return mtu == 0 || (mtu >= 68u && mtu <= 65535u); }
+
+int rxg_tx_encode_frag_dev(rxg_ctx *c, const rxg_txd *d_txd, uint32_t n, const uint8_t *d_payload,
+                           uint32_t mss, uint32_t mtu, uint8_t *d_pkts, uint64_t cap_bytes,
+                           uint32_t slot_bytes, uint32_t *d_off, uint16_t *d_len, uint32_t out_cap,
+                           uint32_t *d_first, uint32_t *d_nseg, uint32_t len_hint, uint32_t flags,
+                           uint32_t *d_totals, void *stream) {
+    RCCHK(dev_ctx(c));
+    if ((slot_bytes & 63u) || (mss & 3u) || !txe_mtu_ok(mtu)) return RXG_EINVAL;
+    if (!d_totals) return RXG_EINVAL;
+    if (n && (!d_txd || !d_pkts || !d_first || !d_nseg || (out_cap && (!d_off || !d_len))))
+        return RXG_EINVAL;
+    if (((uintptr_t)d_txd | (uintptr_t)d_payload | (uintptr_t)d_pkts) & 15u) return RXG_EINVAL;
+    DEVGUARD(c);
+    const hipStream_t s = (hipStream_t)stream;
+    if (n == 0) {
+        HIPCHK(hipMemsetAsync(d_totals, 0, 32, s));
+        return RXG_OK;
+    }
+    int rc = aux_begin(c, txe_frag_ws_bytes(n, out_cap), s);
+    if (rc) return rc;
+    HIPCHK(tx_encode_frag_launch(d_txd, n, d_payload, mss, mtu, d_pkts, cap_bytes, slot_bytes, d_off,
+                                 d_len, out_cap, d_first, d_nseg, len_hint, flags, d_totals, c->d_aux,
+                                 c->tune_txe, c->tune_txe_bpc, s));
+    return aux_end(c, s);
+}
+
+// as rxg_tx_encode_tso, through the same staging buffer:
+// [txd][payload, to its 16-B end][off][len][first][nseg][totals][frames]
+int rxg_tx_encode_frag(rxg_ctx *c, const rxg_txd *txd, uint32_t n, const uint8_t *payload,
+                       uint64_t payload_bytes, uint32_t mss, uint32_t mtu, uint8_t *pkts,
+                       uint64_t cap_bytes, uint32_t *off, uint16_t *len, uint32_t out_cap,
+                       uint32_t *first, uint32_t *nseg, uint32_t flags, uint64_t *span) {
+    if (!c) return RXG_EINVAL;
+    if (span) *span = 0;
+    if (c->device == RXG_HOST_ONLY) return RXG_ENODEV;
+    if ((mss & 3u) || !txe_mtu_ok(mtu)) return RXG_EINVAL;
+    if (n == 0) return RXG_OK;
+    if (!txd || !pkts || !first || !nseg || (out_cap && (!off || !len))) return RXG_EINVAL;
+    uint64_t pay_end = 0; // payload bytes read
+    for (uint32_t k = 0; k < n; ++k) {
+        const rxg_txd &d = txd[k];
+        uint64_t own = 0; // (0 bytes: its kind or lengths skip it, the payload is not read)
+        if (d.kind == RXG_TXD_ARP || d.pay_len == 0) continue;
+        if (rxg_tx_frag_count(&d, 1, mss, mtu, nullptr, &own) || own == 0) continue;
+        const uint64_t e = (uint64_t)d.pay_off16 * 16 + d.pay_len;
+        if (!payload || e > payload_bytes) return RXG_EINVAL;
+        if (e > pay_end) pay_end = e;
+    }
+    uint64_t entries = 0, need = 0; // entries and frame bytes if nothing is skipped
+    int rc = rxg_tx_frag_count(txd, n, mss, mtu, &entries, &need);
+    if (rc) return rc;
+    if (need > cap_bytes) need = cap_bytes;
+    const size_t ne = entries < out_cap ? (size_t)entries : (size_t)out_cap; // entries written
+    DEVGUARD(c);
+    const size_t o_pay = (size_t)n * sizeof(rxg_txd);
+    const size_t o_off = o_pay + ((pay_end + 15u) & ~(size_t)15u);
+    const size_t o_len = o_off + ((ne * 4 + 15u) & ~(size_t)15u);
+    const size_t o_fst = o_len + ((ne * 2 + 15u) & ~(size_t)15u);
+    const size_t o_nsg = o_fst + (((size_t)n * 4 + 15u) & ~(size_t)15u);
+    const size_t o_tot = o_nsg + (((size_t)n * 4 + 15u) & ~(size_t)15u);
+    const size_t o_pkt = (o_tot + 32 + 63u) & ~(size_t)63u;
+    const hipStream_t s = c->stream;
+    rc = ensure_dev_async(&c->d_txe, &c->d_txe_cap, o_pkt + need + 64, s);
+    if (rc) return rc;
+    uint8_t *d = reinterpret_cast<uint8_t *>(c->d_txe);
+    HIPCHK(hipMemcpyAsync(d, txd, o_pay, hipMemcpyHostToDevice, s));
+    if (pay_end) {
+        // (the tail of the last 16-B chunk is read by the kernel and masked)
+        HIPCHK(hipMemsetAsync(d + o_off - 16, 0, 16, s));
+        HIPCHK(hipMemcpyAsync(d + o_pay, payload, pay_end, hipMemcpyHostToDevice, s));
+    }
+    rc = rxg_tx_encode_frag_dev(c, reinterpret_cast<const rxg_txd *>(d), n, d + o_pay, mss, mtu,
+                                d + o_pkt, need, 0, // (= cap_bytes where it binds)
+                                reinterpret_cast<uint32_t *>(d + o_off),
+                                reinterpret_cast<uint16_t *>(d + o_len), (uint32_t)ne,
+                                reinterpret_cast<uint32_t *>(d + o_fst),
+                                reinterpret_cast<uint32_t *>(d + o_nsg),
+                                (uint32_t)(need / (ne ? ne : 1)), flags,
+                                reinterpret_cast<uint32_t *>(d + o_tot), s);
     if (rc) return rc;
     uint32_t tot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     HIPCHK(hipMemcpyAsync(tot, d + o_tot, 32, hipMemcpyDeviceToHost, s));

@@ -29,6 +29,10 @@
 // TCP segmentation (rxg_tx_encode_tso_dev) is a sibling of both halves further
 // down: a layout pass over entries and units, and tx_encode_tso_kernel with a
 // lane group per entry.  The kernels above it are not touched by it.
+//
+// IPv4 fragmentation of UDP datagrams (rxg_tx_encode_frag_dev) is the same pair
+// once more, with both cuts in one place (txe_frag_cut_of), and a finish kernel
+// that adds the fragments' partial sums into the datagram's one UDP checksum.
 #include <hip/hip_runtime.h>
 
 #include "rx_common.h"
@@ -321,11 +325,20 @@ __device__ __forceinline__ uint4 txe_src(const txe_frame &f, int32_t a) {
     return v;
 }
 
-template <int G, int P, int NB, bool TSO = false>
+// IPv4 fragmentation (rxg_tx_encode_frag_dev, further down): what an entry that
+// is one fragment of a cut UDP datagram adds to its frame
+struct txe_fragx {
+    uint32_t mode;  // 0: not a fragment; 1: fragment 0 (42-B header); 2: a later one (34-B header)
+    uint32_t id_fo; // IPv4 id | flags / offset << 16, host order
+    uint32_t dlen;  // the datagram's length (8 + pay_len)
+    uint32_t *psum; // the entry's partial-sum word
+};
+
+template <int G, int P, int NB, bool TSO = false, bool FRAG = false>
 __device__ __forceinline__ void txe_frame_run(const txe_frame &f, uint4 d0, uint4 d1, uint4 d2,
                                               uint32_t kind, uint32_t fl, uint4 (&own)[P],
                                               uint4 (&prv)[NB ? 1 : P], uint32_t gl, uint32_t lane,
-                                              bool no_cksum) {
+                                              bool no_cksum, const txe_fragx *x = nullptr) {
     static_assert(G >= 4, "sector 0 is held by lanes 0..3 of pass 0");
     constexpr int32_t STEP = 16 * G;
     const int32_t s0 = 16 * (int32_t)gl;
@@ -345,7 +358,19 @@ __device__ __forceinline__ void txe_frame_run(const txe_frame &f, uint4 d0, uint
         }
         uint4 v = txe_funnel(lo, own[q], f.k);
         if (q == 0) {
-            const uint4 h = txe_header(gl, d0, d1, d2, kind, fl);
+            uint4 h = txe_header(gl, d0, d1, d2, kind, fl);
+            if constexpr (FRAG) {
+                if (x->mode) { // id and flags / offset; the datagram's length, or no UDP header
+                    if (gl == 1) {
+                        h.x |= rx_bswap16(x->id_fo & 0xFFFFu) << 16;
+                        h.y |= rx_bswap16(x->id_fo >> 16);
+                    }
+                    if (gl == 2) {
+                        h.y = x->mode == 1 ? (h.y & 0xFFFFu) | (rx_bswap16(x->dlen) << 16) : 0u;
+                        if (x->mode == 2) h.x &= 0xFFFFu;
+                    }
+                }
+            }
             v.x |= h.x, v.y |= h.y, v.z |= h.z, v.w |= h.w;
             // IPv4 header words [14, 34), the checksum field (24, 25) is 0
             if (gl == 0) ip = v.w >> 16;
@@ -357,6 +382,12 @@ __device__ __forceinline__ void txe_frame_run(const txe_frame &f, uint4 d0, uint
         if (q == 0) {
             if (gl == 0) v = make_uint4(0, 0, 0, 0);
             if (gl == 1) v.x = v.y = 0, v.z &= 0xFFFF0000u;
+            if constexpr (FRAG) {
+                if (x->mode == 2) { // datagram bytes only, [34, fl): the addresses count in fragment 0
+                    if (gl == 1) v.z = v.w = 0;
+                    if (gl == 2) v.x &= 0xFFFF0000u;
+                }
+            }
         }
         acc = add_halves(add_halves(add_halves(add_halves(acc, v.x), v.y), v.z), v.w);
     }
@@ -393,9 +424,16 @@ __device__ __forceinline__ void txe_frame_run(const txe_frame &f, uint4 d0, uint
         // rte_ipv4_cksum as compiled into the reference: the plain complement
         // (a header summing to 0xFFFF stores 0), see tx_cksum.hip
         const uint32_t hip = ~fold16(ip) & 0xFFFFu;
+        if constexpr (FRAG) {
+            // a fragment's sum of its datagram bytes; the checksum is txe_frag_finish_kernel's
+            if (x->mode && gl == 0) *x->psum = fold16(acc);
+        }
         acc += (proto << 8) + rx_bswap16(l4n); // pseudo-header {0, proto}, be16(l4 len)
         uint32_t kl4 = (~fold16(acc)) & 0xFFFFu; // rte_ipv4_udptcp_cksum, rte_ip.h:325-349
         if (kl4 == 0u && proto == 17u) kl4 = 0xFFFFu;
+        if constexpr (FRAG) {
+            if (x->mode) kl4 = 0u;
+        }
         if (gl == 1) own[0].z |= hip;                     // bytes 24,25
         if (gl == 2 && proto == 17u) own[0].z |= kl4;     // 40,41
         if (gl == 3 && proto == 6u) own[0].x |= kl4 << 16; // 50,51
@@ -859,6 +897,304 @@ static const txe_tso_launch_fn k_txe_tso[] = {
 static_assert(sizeof(k_txe_tso) / sizeof(k_txe_tso[0]) == sizeof(k_txe) / sizeof(k_txe[0]),
               "one TSO kernel per k_txe entry");
 
+// ---- IPv4 fragmentation of UDP datagrams (rxg_tx_encode_frag_dev) -------------
+// The second cut: a UDP descriptor whose datagram (L = 8 + pay_len bytes, the
+// UDP header included) does not fit the IPv4 MTU becomes s fragments of
+// fp = (mtu - 20) & ~7 datagram bytes.  Fragment 0 is the 42-B header and the
+// payload from its start; fragment j > 0 a 34-B header and the payload from
+// D = j * fp - 8, a multiple of 8: hc / k / lo from 34 - (D & 15) as TSO takes
+// them from hdr - (D & 15), and the payload still lands 2 mod 4.  The layout
+// pass is the TSO one with txe_frag_cut_of in txe_cut_of's place.  The one
+// UDP checksum of a cut datagram covers bytes that s lane groups write: each
+// leaves the folded sum of its datagram bytes in a workspace word per entry
+// (fragment 0 with the address words, as every frame's sum has them), and
+// txe_frag_finish_kernel adds them up behind the encoder and stores the two
+// bytes at offset 40 of fragment 0.
+
+// txe_cut_of with both cuts; *fp = the fragment's datagram bytes, 0 = not a cut
+// UDP datagram (one place: sums, layout, entries and the encoder ask it)
+__device__ __forceinline__ txe_cut txe_frag_cut_of(uint4 d2, uint32_t mss, uint32_t mtu,
+                                                   uint32_t slot, uint32_t *fp) {
+    const uint32_t kind = d2.y >> 24, pay = d2.w;
+    *fp = 0;
+    if (kind != RXG_TXD_UDP || mtu == 0 || 28ull + pay <= mtu) return txe_cut_of(d2, mss, slot);
+    const uint32_t f = (mtu - 20u) & ~7u;
+    *fp = f;
+    txe_cut c;
+    c.s = 0, c.full = c.last = 0;
+    if (28ull + pay > 65535ull) return c; // no IPv4 datagram is that long
+    const uint32_t L = 8u + pay, s = (L + f - 1u) / f; // (L > mtu - 20 >= f: s >= 2)
+    const uint32_t full = 34u + f;
+    if (full > 65535u || (slot && full > slot)) return c;
+    c.s = s, c.full = full, c.last = 34u + (L - (s - 1u) * f);
+    return c;
+}
+
+__global__ __launch_bounds__(256) void txe_frag_sums_kernel(const uint4 *__restrict__ txd, uint32_t n,
+                                                            uint32_t mss, uint32_t mtu, uint32_t slot,
+                                                            unsigned long long *__restrict__ sums_e,
+                                                            unsigned long long *__restrict__ sums_u) {
+    __shared__ unsigned long long pe[4], pu[4];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t c0 = (uint64_t)blockIdx.x * TXE_CHUNK;
+    unsigned long long se = 0, su = 0;
+    for (uint32_t k = 0; k < TXE_PER_THREAD; ++k) {
+        const uint64_t q = c0 + (uint64_t)k * 256 + tid;
+        if (q < n) {
+            uint32_t fp;
+            const txe_cut c = txe_frag_cut_of(txd[3 * q + 2], mss, mtu, slot, &fp);
+            se += c.s ? c.s : 1ull;
+            su += txe_cut_units(c);
+        }
+    }
+    se = wave_sum64(se), su = wave_sum64(su);
+    if ((tid & 63u) == 0) pe[tid >> 6] = se, pu[tid >> 6] = su;
+    __syncthreads();
+    if (tid == 0) {
+        sums_e[blockIdx.x] = pe[0] + pe[1] + pe[2] + pe[3];
+        sums_u[blockIdx.x] = pu[0] + pu[1] + pu[2] + pu[3];
+    }
+}
+
+// txe_tso_layout_kernel with both cuts
+__global__ __launch_bounds__(256) void txe_frag_layout_kernel(
+    const uint4 *__restrict__ txd, uint32_t n, uint32_t mss, uint32_t mtu, uint32_t slot,
+    const unsigned long long *__restrict__ base_e, const unsigned long long *__restrict__ base_u,
+    unsigned long long cap, unsigned long long out_cap,
+    uint32_t *__restrict__ first, uint32_t *__restrict__ nseg, uint32_t *__restrict__ posu,
+    uint32_t nchunks, txe_tso_part *__restrict__ part) {
+    __shared__ unsigned long long run_e, run_u, we[4], wu[4];
+    __shared__ unsigned long long s_end[4], s_fr[4], s_ds[4];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    unsigned long long frames = 0, descs = 0, end = 0;
+    for (uint32_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+        if (tid == 0) run_e = base_e[chunk], run_u = base_u[chunk]; // (read after the first barrier)
+        const uint64_t c0 = (uint64_t)chunk * TXE_CHUNK;
+        for (uint32_t k = 0; k < TXE_PER_THREAD; ++k) {
+            const uint64_t q = c0 + (uint64_t)k * 256 + tid;
+            txe_cut c;
+            c.s = 0, c.full = c.last = 0;
+            uint32_t fp;
+            if (q < n) c = txe_frag_cut_of(txd[3 * q + 2], mss, mtu, slot, &fp);
+            const unsigned long long ne = q < n ? (c.s ? c.s : 1ull) : 0ull, u = txe_cut_units(c);
+            unsigned long long xe = ne, xu = u; // inclusive wave scans
+            for (uint32_t o = 1; o < 64; o <<= 1) {
+                const unsigned long long ye = __shfl_up(xe, o), yu = __shfl_up(xu, o);
+                if (lane >= o) xe += ye, xu += yu;
+            }
+            if (lane == 63) we[wv] = xe, wu[wv] = xu;
+            __syncthreads();
+            unsigned long long fe = run_e + xe - ne, pu = run_u + xu - u;
+            for (uint32_t w = 0; w < wv; ++w) fe += we[w], pu += wu[w];
+            if (q < n) {
+                bool ok = c.s != 0 && fe + c.s <= out_cap;
+                if (ok) ok = slot ? (fe + c.s) * slot <= cap : ((pu + u) << 6) <= cap;
+                first[q] = fe > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)fe;
+                nseg[q] = ok ? (uint32_t)c.s : 0u;
+                posu[q] = (uint32_t)pu; // (a written descriptor's frames end below 2^32 units)
+                const unsigned long long fu = (c.full + 63u) >> 6, su = slot >> 6;
+                if (ok) {
+                    const unsigned long long at = slot ? (fe + c.s - 1) * su : pu + (c.s - 1) * fu;
+                    const unsigned long long en = at + ((c.last + 63u) >> 6);
+                    frames += c.s, descs += 1;
+                    if (en > end) end = en;
+                }
+            }
+            __syncthreads();
+            if (tid == 0) {
+                run_e += we[0] + we[1] + we[2] + we[3];
+                run_u += wu[0] + wu[1] + wu[2] + wu[3];
+            }
+            __syncthreads();
+        }
+    }
+    frames = wave_sum64(frames), descs = wave_sum64(descs);
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long y = __shfl_xor(end, o);
+        end = y > end ? y : end;
+    }
+    if (lane == 0) s_end[wv] = end, s_fr[wv] = frames, s_ds[wv] = descs;
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 4; ++w) end = s_end[w] > end ? s_end[w] : end;
+        part[blockIdx.x].end_units = end;
+        part[blockIdx.x].frames = s_fr[0] + s_fr[1] + s_fr[2] + s_fr[3];
+        part[blockIdx.x].descs = s_ds[0] + s_ds[1] + s_ds[2] + s_ds[3];
+    }
+}
+
+// txe_tso_entries_kernel with both cuts: entry j of a written descriptor is
+// c.full bytes long but the last, and the frames follow each other
+__global__ __launch_bounds__(256) void txe_frag_entries_kernel(
+    const uint4 *__restrict__ txd, uint32_t n, uint32_t mss, uint32_t mtu, uint32_t slot,
+    const uint32_t *__restrict__ first, const uint32_t *__restrict__ nseg,
+    const uint32_t *__restrict__ posu, const unsigned long long *__restrict__ need,
+    unsigned long long out_cap, uint32_t *__restrict__ off, uint16_t *__restrict__ len,
+    uint32_t *__restrict__ map) {
+    const unsigned long long ne = *need < out_cap ? *need : out_cap;
+    for (unsigned long long e = (unsigned long long)blockIdx.x * 256 + threadIdx.x; e < ne;
+         e += (unsigned long long)gridDim.x * 256) {
+        // first[0] == 0 <= e; descriptor q owns at least one entry, so q <= e
+        uint32_t lo = 0, hi = e < n - 1 ? (uint32_t)e : n - 1;
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo + 1) >> 1);
+            if (first[mid] <= e) lo = mid;
+            else hi = mid - 1;
+        }
+        const uint32_t q = lo, s = nseg[q], j = (uint32_t)e - first[q];
+        uint32_t o = 0, l = 0;
+        if (s) {
+            uint32_t fp;
+            const txe_cut c = txe_frag_cut_of(txd[3 * (uint64_t)q + 2], mss, mtu, slot, &fp);
+            l = j + 1 == s ? c.last : c.full;
+            o = slot ? (uint32_t)(e * (slot >> 6)) : posu[q] + j * ((c.full + 63u) >> 6);
+        }
+        map[e] = q;
+        off[e] = o;
+        len[e] = (uint16_t)l;
+    }
+}
+
+// tx_encode_tso_kernel with both cuts: an entry of a cut UDP datagram is one
+// fragment, and leaves its partial sum in psum[e]
+template <int G, int P, int FPG, int NB>
+__global__ __launch_bounds__(256) void tx_encode_frag_kernel(
+    const uint4 *__restrict__ txd, const uint8_t *__restrict__ pay, uint8_t *__restrict__ pkts,
+    const uint32_t *__restrict__ off, const uint16_t *__restrict__ len,
+    const uint32_t *__restrict__ map, const uint32_t *__restrict__ first,
+    const unsigned long long *__restrict__ need, unsigned long long out_cap, uint32_t mss,
+    uint32_t mtu, uint32_t *__restrict__ psum, uint32_t flags) {
+    constexpr uint32_t GPB = 256 / G, TILE = GPB * FPG;
+    constexpr int32_t STEP = 16 * G;
+    const uint32_t tid = threadIdx.x, gl = tid & (G - 1), grp = tid / G, lane = tid & 63u;
+    const int32_t s0 = 16 * (int32_t)gl;
+    const unsigned long long ne = *need < out_cap ? *need : out_cap; // entries laid out
+    for (uint64_t tile = blockIdx.x; tile * TILE < ne; tile += gridDim.x) {
+        txe_frame f[FPG];
+        txe_fragx x[FPG];
+        uint4 d0[FPG], d1[FPG], d2[FPG];
+        uint32_t kind[FPG], fl[FPG];
+        uint4 own[FPG][P], prv[FPG][NB ? 1 : P];
+#pragma unroll
+        for (int i = 0; i < FPG; ++i) {
+            const uint64_t pos = tile * TILE + (uint64_t)i * GPB + grp;
+            const uint64_t e = pos < ne ? pos : 0;
+            fl[i] = pos < ne ? (uint32_t)len[e] : 0u;
+            const uint64_t q = map[e];
+            const uint32_t j = (uint32_t)e - first[q];
+            d0[i] = txd[3 * q], d1[i] = txd[3 * q + 1], d2[i] = txd[3 * q + 2];
+            kind[i] = d2[i].y >> 24;
+            uint32_t hdr = kind[i] == RXG_TXD_TCP ? 54u + 4u * ((d2[i].y >> 16) & 0xFFu) : 42u;
+            uint32_t dd = 0; // the entry's first byte in the payload
+            const uint32_t fp = kind[i] == RXG_TXD_UDP && mtu && 28ull + d2[i].w > mtu
+                                    ? (mtu - 20u) & ~7u : 0u; // (as txe_frag_cut_of)
+            x[i].mode = 0, x[i].id_fo = 0, x[i].dlen = 0, x[i].psum = psum + e;
+            if (fp && fl[i]) {
+                const uint32_t at = j * fp, L = 8u + d2[i].w;
+                x[i].mode = j ? 2u : 1u;
+                x[i].dlen = L;
+                x[i].id_fo = (d1[i].z & 0xFFFFu) | (((at >> 3) | (at + fp < L ? 0x2000u : 0u)) << 16);
+                if (j) hdr = 34u, dd = at - 8u;
+            }
+            const uint32_t seg = (fl[i] == 0 || kind[i] == RXG_TXD_ARP) ? 0u : fl[i] - hdr;
+            if (kind[i] == RXG_TXD_TCP && mss) {
+                dd = j * mss;
+                d1[i].z += dd;
+                if ((uint64_t)dd + seg < d2[i].w) d2[i].y &= ~(0x09u << 8); // not the last: FIN, PSH
+            }
+            const uint32_t r = dd & 15u, hv = hdr - r;
+            f[i].fb = pkts + ((uint64_t)off[e] << 6);
+            f[i].pb = pay + ((uint64_t)d2[i].z << 4) + (dd & ~15u);
+            f[i].plen = seg ? (int32_t)(r + seg) : 0;
+            f[i].lo = (int32_t)r;
+            f[i].hc = (int32_t)((hv + 15u) >> 4);
+            f[i].k = ((16u - (hv & 15u)) - 2u) >> 2;
+            f[i].nb = (int32_t)((fl[i] + 63u) & ~63u);
+        }
+#pragma unroll
+        for (int i = 0; i < FPG; ++i)
+#pragma unroll
+            for (int q = 0; q < P; ++q) {
+                const int32_t a = ((s0 + q * STEP) >> 4) - f[i].hc + 1;
+                own[i][q] = txe_src<NB != 0, true>(f[i], a);
+                if constexpr (!NB) prv[i][q] = txe_src<false, true>(f[i], a - 1);
+            }
+#pragma unroll
+        for (int i = 0; i < FPG; ++i)
+            txe_frame_run<G, P, NB, true, true>(f[i], d0[i], d1[i], d2[i], kind[i], fl[i], own[i],
+                                                prv[i], gl, lane, (flags & RXG_TXE_NO_CKSUM) != 0,
+                                                &x[i]);
+    }
+}
+
+// the UDP checksum of every cut datagram that was written: a group of FIN_G
+// lanes per descriptor adds its s partial sums (s <= 1365: 86 trips of the
+// group, not 1365 of a thread), the protocol and be16(L), and stores the two
+// bytes at offset 40 of fragment 0.  Skipped and uncut descriptors write nothing.
+constexpr uint32_t FIN_G = 16;
+__global__ __launch_bounds__(256) void txe_frag_finish_kernel(
+    const uint4 *__restrict__ txd, uint32_t n, uint32_t mtu, const uint32_t *__restrict__ first,
+    const uint32_t *__restrict__ nseg, const uint32_t *__restrict__ off,
+    const uint32_t *__restrict__ psum, uint8_t *__restrict__ pkts) {
+    const uint32_t gl = threadIdx.x & (FIN_G - 1);
+    for (uint64_t q = ((uint64_t)blockIdx.x * 256 + threadIdx.x) / FIN_G; q < n;
+         q += (uint64_t)gridDim.x * (256 / FIN_G)) { // group-uniform
+        const uint4 d2 = txd[3 * q + 2];
+        const uint32_t s = nseg[q];
+        if (d2.y >> 24 != RXG_TXD_UDP || 28ull + d2.w <= mtu || s == 0) continue;
+        const uint32_t e0 = first[q];
+        uint32_t acc = 0; // (s sums below 2^16 each)
+        for (uint32_t j = gl; j < s; j += FIN_G) acc += psum[e0 + j];
+        for (uint32_t o = FIN_G / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+        if (gl == 0) {
+            acc += (17u << 8) + rx_bswap16(8u + d2.w); // pseudo-header {0, 17}, be16(L)
+            uint32_t k = ~fold16(acc) & 0xFFFFu;
+            if (k == 0u) k = 0xFFFFu;
+            *reinterpret_cast<uint16_t *>(pkts + ((uint64_t)off[e0] << 6) + 40) = (uint16_t)k;
+        }
+    }
+}
+
+template <int G, int P, int FPG, int NB>
+hipError_t launch_txe_frag(const uint4 *txd, const uint8_t *pay, uint8_t *pkts, const uint32_t *off,
+                           const uint16_t *len, const uint32_t *map, const uint32_t *first,
+                           const unsigned long long *need, uint32_t out_cap, uint32_t mss,
+                           uint32_t mtu, uint32_t *psum, uint32_t flags, uint32_t bpc_cap,
+                           hipStream_t s) {
+    constexpr uint32_t TILE = (256 / G) * FPG;
+    int cu = 0, occ = 0;
+    hipError_t e = rx_occupancy(reinterpret_cast<const void *>(tx_encode_frag_kernel<G, P, FPG, NB>),
+                                256, 0, &cu, &occ);
+    if (e != hipSuccess) return e;
+    // as launch_txe_tso: the grid is sized for out_cap
+    const uint64_t tiles = ((uint64_t)out_cap + TILE - 1) / TILE;
+    uint64_t bpc = (uint64_t)occ;
+    if (bpc_cap && bpc > bpc_cap) bpc = bpc_cap;
+    uint64_t blocks = (uint64_t)cu * bpc;
+    if (blocks > tiles || bpc_cap == TXE_FULL_GRID) blocks = tiles;
+    if (blocks > 0x7FFFFFFFull) blocks = 0x7FFFFFFFull; // (the tile loop strides)
+    if (blocks == 0) return hipSuccess;
+    hipLaunchKernelGGL((tx_encode_frag_kernel<G, P, FPG, NB>), dim3((uint32_t)blocks), dim3(256), 0, s,
+                       txd, pay, pkts, off, len, map, first, need, (unsigned long long)out_cap, mss,
+                       mtu, psum, flags);
+    return hipGetLastError();
+}
+
+typedef hipError_t (*txe_frag_launch_fn)(const uint4 *, const uint8_t *, uint8_t *, const uint32_t *,
+                                         const uint16_t *, const uint32_t *, const uint32_t *,
+                                         const unsigned long long *, uint32_t, uint32_t, uint32_t,
+                                         uint32_t *, uint32_t, uint32_t, hipStream_t);
+// the shapes of k_txe, index for index (rxg_tune_txe and len_hint choose all three)
+static const txe_frag_launch_fn k_txe_frag[] = {
+    launch_txe_frag<4, 1, 4, 1>,  launch_txe_frag<4, 2, 2, 1>,  launch_txe_frag<8, 12, 1, 1>,
+    launch_txe_frag<16, 8, 1, 1>, launch_txe_frag<4, 1, 4, 0>,  launch_txe_frag<4, 2, 2, 0>,
+    launch_txe_frag<8, 12, 1, 0>, launch_txe_frag<16, 8, 1, 0>, launch_txe_frag<4, 1, 1, 1>,
+    launch_txe_frag<8, 1, 1, 1>,  launch_txe_frag<8, 4, 2, 1>,  launch_txe_frag<16, 6, 1, 1>,
+    launch_txe_frag<32, 4, 1, 1>, launch_txe_frag<32, 4, 1, 0>, launch_txe_frag<8, 1, 1, 0>,
+};
+static_assert(sizeof(k_txe_frag) / sizeof(k_txe_frag[0]) == sizeof(k_txe) / sizeof(k_txe[0]),
+              "one fragmenting kernel per k_txe entry");
+
 // the variant a len_hint chooses: the fastest of each class (k_txe's comment);
 // K2's class boundaries
 inline uint32_t txe_default_variant(uint32_t len_hint) {
@@ -917,6 +1253,61 @@ hipError_t tx_encode_tso_launch(const void *txd_, uint32_t n, const uint8_t *pay
     if (variant < txe_num_variants()) v = variant;
     return k_txe_tso[v](txd, pay, pkts, off, len, map, first, sums_e + nchunks, out_cap, mss, flags,
                         bpc_cap ? bpc_cap : k_txe[v].bpc, s);
+}
+
+// txe_tso_ws_bytes plus a partial-sum word per entry
+size_t txe_frag_ws_bytes(uint32_t n, uint32_t out_cap) {
+    return ((txe_tso_ws_bytes(n, out_cap) + 15u) & ~(size_t)15u) + (uint64_t)out_cap * 4;
+}
+
+// the layout pass with both cuts, the encoder over the entries, then the cut
+// datagrams' checksums; variant / bpc_cap as tx_encode_launch
+hipError_t tx_encode_frag_launch(const void *txd_, uint32_t n, const uint8_t *pay, uint32_t mss,
+                                 uint32_t mtu, uint8_t *pkts, uint64_t cap, uint32_t slot,
+                                 uint32_t *off, uint16_t *len, uint32_t out_cap, uint32_t *first,
+                                 uint32_t *nseg, uint32_t len_hint, uint32_t flags, uint32_t *totals,
+                                 void *ws, uint32_t variant, uint32_t bpc_cap, hipStream_t s) {
+    const uint4 *txd = reinterpret_cast<const uint4 *>(txd_);
+    const uint32_t nchunks = (uint32_t)(((uint64_t)n + TXE_CHUNK - 1) / TXE_CHUNK);
+    unsigned long long *sums_e = reinterpret_cast<unsigned long long *>(ws);
+    unsigned long long *sums_u = sums_e + nchunks + 1;
+    txe_tso_part *part = reinterpret_cast<txe_tso_part *>(sums_u + nchunks + 1);
+    uint32_t *posu = reinterpret_cast<uint32_t *>(part + TXE_PARTS);
+    uint32_t *map = posu + n;
+    uint32_t *psum = reinterpret_cast<uint32_t *>(
+        reinterpret_cast<uint8_t *>(ws) + ((txe_tso_ws_bytes(n, out_cap) + 15u) & ~(size_t)15u));
+    const uint32_t nparts = nchunks < TXE_PARTS ? nchunks : TXE_PARTS;
+    hipError_t e = hipSuccess;
+    const uint64_t lim = 64ull << 32; // offsets are 32 bits of 64-B units
+    if (cap > lim) cap = lim;
+    hipLaunchKernelGGL(txe_frag_sums_kernel, dim3(nchunks), dim3(256), 0, s, txd, n, mss, mtu, slot,
+                       sums_e, sums_u);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(txe_tso_scan_kernel, dim3(2), dim3(1024), 0, s, sums_e, (uint64_t)nchunks);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(txe_frag_layout_kernel, dim3(nparts), dim3(256), 0, s, txd, n, mss, mtu, slot,
+                       sums_e, sums_u, (unsigned long long)cap, (unsigned long long)out_cap, first,
+                       nseg, posu, nchunks, part);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (out_cap) { // (sized for out_cap: the entry count is on the device)
+        const uint64_t eb = ((uint64_t)out_cap + 255) / 256;
+        hipLaunchKernelGGL(txe_frag_entries_kernel, dim3((uint32_t)(eb < 16384 ? eb : 16384)),
+                           dim3(256), 0, s, txd, n, mss, mtu, slot, first, nseg, posu,
+                           sums_e + nchunks, (unsigned long long)out_cap, off, len, map);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(txe_tso_totals_kernel, dim3(1), dim3(256), 0, s, part, nparts, n,
+                       sums_e + nchunks, totals);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    uint32_t v = txe_default_variant(len_hint);
+    if (variant < txe_num_variants()) v = variant;
+    e = k_txe_frag[v](txd, pay, pkts, off, len, map, first, sums_e + nchunks, out_cap, mss, mtu, psum,
+                      flags, bpc_cap ? bpc_cap : k_txe[v].bpc, s);
+    if (e != hipSuccess || mtu == 0 || out_cap == 0 || (flags & RXG_TXE_NO_CKSUM)) return e;
+    const uint64_t fb = ((uint64_t)n * FIN_G + 255) / 256;
+    hipLaunchKernelGGL(txe_frag_finish_kernel, dim3((uint32_t)(fb < 16384 ? fb : 16384)), dim3(256), 0,
+                       s, txd, n, mtu, first, nseg, off, psum, pkts);
+    return hipGetLastError();
 }
 
 uint32_t txe_num_variants() { return (uint32_t)(sizeof(k_txe) / sizeof(k_txe[0])); }

@@ -1167,6 +1167,9 @@ static int g_tx_encode;
 static atomic_ullong g_txe_frames;
 static uint32_t g_tx_mss;
 static atomic_ullong g_tso_frags;
+static uint32_t g_tx_mtu;
+static uint16_t g_ip_id;
+static atomic_ullong g_udp_frags;
 static void tx_stage_free(void);
 
 /* ---- lifecycle ---------------------------------------------------------- */
@@ -1287,6 +1290,9 @@ void nstack_fini(void) {
     atomic_store_explicit(&g_txe_frames, 0, memory_order_relaxed);
     g_tx_mss = 0;
     atomic_store_explicit(&g_tso_frags, 0, memory_order_relaxed);
+    g_tx_mtu = 0;
+    g_ip_id = 1;
+    atomic_store_explicit(&g_udp_frags, 0, memory_order_relaxed);
     tx_stage_free();
     g_mb_release = NULL;
     g_mb_arg = NULL;
@@ -3801,6 +3807,9 @@ int nstack_arp_insert(uint32_t ip, const uint8_t mac[6]) {
     return r;
 }
 
+static void tx_place(uint8_t *fp, uint32_t fl, uint64_t *pos, uint32_t *off, uint16_t *len,
+                     uint32_t *n);
+
 /* ---- TX through the GPU encoder (K5, nstack_set_tx_encode): the walks of
  * nstack_tx_burst fill send descriptors instead of frames, the payloads go
  * into a staging buffer (pinned through rxg_register_host where the context
@@ -3818,6 +3827,77 @@ static uint32_t g_tx_mss;
 static atomic_ullong g_tso_frags; /* stat 14 */
 static uint32_t *s_txseg;         /* rxg_tx_encode_tso's first / nseg */
 static uint32_t s_txseg_cap;
+/* IPv4 fragmentation (nstack_set_tx_mtu): udp_out's walk sends a datagram that
+ * does not fit the MTU as its fragments; 0 = off.  The id of the next cut
+ * datagram: 1 after init or fini */
+static uint32_t g_tx_mtu;
+static uint16_t g_ip_id = 1;
+static atomic_ullong g_udp_frags; /* stat 25 */
+
+int nstack_set_tx_mtu(uint32_t mtu) {
+    if (mtu && (mtu < 68u || mtu > 65535u)) return RXG_EINVAL;
+    pthread_mutex_lock(&g_lock);
+    g_tx_mtu = mtu;
+    pthread_mutex_unlock(&g_lock);
+    return 0;
+}
+
+static uint32_t raw_sum16(const uint8_t *p, uint32_t n, uint32_t s) {
+    uint32_t i = 0;
+    for (; i + 1 < n; i += 2) s += (uint32_t)p[i] | ((uint32_t)p[i + 1] << 8);
+    if (i < n) s += p[i];
+    return s;
+}
+static uint16_t fold_not16(uint32_t s) {
+    s = (s >> 16) + (s & 0xFFFFu);
+    s = (s >> 16) + (s & 0xFFFFu);
+    return (uint16_t)~s;
+}
+
+/* the s fragments of datagram o (fp datagram bytes each, include/rxgpu.h) from
+ * *pos on; cksum: every header checksum and the datagram's UDP checksum filled
+ * here (rxg_tx_cksum knows whole datagrams only) */
+static void enc_udp_frags(uint8_t *pkts, const uint8_t *src_mac, const uint8_t *dst_mac,
+                          const struct offload *o, uint32_t fp, uint32_t s, uint16_t id, int cksum,
+                          uint64_t *pos, uint32_t *off, uint16_t *len, uint32_t *n) {
+    const uint32_t L = 8u + (uint32_t)o->length;
+    uint16_t k16 = 0;
+    if (cksum) { /* rte_ipv4_udptcp_cksum over the whole datagram, 0 -> 0xFFFF */
+        uint8_t h[20];
+        wr32(h, o->sip), wr32(h + 4, o->dip);
+        h[8] = 0, h[9] = IPPROTO_UDP;
+        wr16be(h + 10, L);
+        memcpy(h + 12, &o->sport, 2), memcpy(h + 14, &o->dport, 2);
+        wr16be(h + 16, L);
+        h[18] = h[19] = 0;
+        k16 = fold_not16(raw_sum16(o->data, o->length, raw_sum16(h, 20, 0)));
+        if (!k16) k16 = 0xFFFF;
+    }
+    for (uint32_t j = 0; j < s; j++) {
+        const uint32_t at = j * fp, b = j + 1 == s ? L - at : fp, fl = 34u + b;
+        uint8_t *m = pkts + *pos;
+        memcpy(m, dst_mac, 6);
+        memcpy(m + 6, src_mac, 6);
+        wr16be(m + 12, 0x0800);
+        enc_ipv4(m + 14, fl, IPPROTO_UDP, o->sip, o->dip);
+        wr16be(m + 18, id);
+        wr16be(m + 20, (at >> 3) | (j + 1 < s ? 0x2000u : 0u));
+        if (cksum) {
+            const uint16_t hip = fold_not16(raw_sum16(m + 14, 20, 0)); /* the plain complement */
+            memcpy(m + 24, &hip, 2);
+        }
+        uint32_t done = 0;
+        if (j == 0) {
+            memcpy(m + 34, &o->sport, 2);
+            memcpy(m + 36, &o->dport, 2);
+            wr16be(m + 38, L);
+            memcpy(m + 40, &k16, 2);
+            done = 8;
+        }
+        if (b > done) memcpy(m + 34 + done, o->data + (at + done - 8u), b - done);
+        tx_place(m, fl, pos, off, len, n);
+    }
+}
 
 int nstack_set_tx_mss(uint32_t mss) {
     if (mss & 3u) return RXG_EINVAL;
@@ -3909,7 +3989,8 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
     uint32_t n = 0, nd = 0; /* frames; the encoder's descriptors */
     uint64_t pos = 0;
     int full = 0;
-    const uint32_t mss = g_tx_mss;
+    const uint32_t mss = g_tx_mss, mtu = g_tx_mtu;
+    uint32_t nfrag = 0; /* host-framed fragments: complete frames, not rxg_tx_cksum's */
     /* the GPU encoder: descriptors instead of frames (same walks, same rules) */
     int enc = g_tx_encode && cksum && max_frames;
     if (enc) {
@@ -3922,7 +4003,7 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
             }
             s_txd = t, s_txd_cap = max_frames;
         }
-        if (mss && s_txseg_cap < max_frames) {
+        if ((mss || mtu) && s_txseg_cap < max_frames) {
             uint32_t *t = realloc(s_txseg, (size_t)max_frames * 2 * sizeof(*t));
             if (!t) {
                 pthread_mutex_unlock(&g_lock);
@@ -3959,6 +4040,43 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
             continue;
         }
         const uint8_t *dmac = arp_lookup(o->dip);
+        if (dmac && mtu && 28ull + o->length > mtu) {
+            /* cut at the MTU: its s fragments go out now, all or none */
+            const uint32_t L = 8u + (uint32_t)o->length, fp = (mtu - 20u) & ~7u;
+            const uint32_t s = (L + fp - 1u) / fp;
+            const uint64_t bytes = (uint64_t)(s - 1u) * align64(34u + fp) +
+                                   align64(34u + (L - (s - 1u) * fp));
+            if (28ull + o->length > 65535u || 34u + fp > 65535u || s > max_frames ||
+                bytes > cap_bytes) { /* no pass of this size can carry it: dropped */
+                ring_dequeue(h->sndbuf, (void **)&o);
+                pthread_mutex_unlock(&h->mutex);
+                free(o->data);
+                free(o);
+                g_stat[1]++;
+                continue;
+            }
+            if (n + s > max_frames || pos + bytes > cap_bytes || (enc && !tx_stage_room(o->length))) {
+                pthread_mutex_unlock(&h->mutex);
+                full = 1;
+                break;
+            }
+            ring_dequeue(h->sndbuf, (void **)&o);
+            pthread_mutex_unlock(&h->mutex);
+            const uint16_t id = g_ip_id++;
+            if (enc) { /* one descriptor: the encoder cuts it the same way */
+                tx_describe(RXG_TXD_UDP, h->localmac, dmac, o->sip, o->dip, NULL, o->sport, o->dport,
+                            o->data, o->length, bytes, &pos, &nd);
+                s_txd[nd - 1].seq = id;
+                n += s;
+            } else {
+                enc_udp_frags(pkts, h->localmac, dmac, o, fp, s, id, cksum, &pos, off, len, &n);
+                nfrag += s;
+            }
+            atomic_fetch_add_explicit(&g_udp_frags, 1, memory_order_relaxed);
+            free(o->data);
+            free(o);
+            continue;
+        }
         const uint32_t fl = dmac ? 42u + o->length : 42u;
         if (fl > 65535u) { /* no frame can carry it: dropped */
             ring_dequeue(h->sndbuf, (void **)&o);
@@ -4130,7 +4248,11 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
         const uint32_t nw = n - n0;
         if (enc) { /* K5 on the GPU: the frames, off and len of the walks' descriptors */
             uint64_t used = 0;
-            if (mss) /* nw entries from nd descriptors */
+            if (mtu) /* nw entries from nd descriptors, both cuts */
+                rc = rxg_tx_encode_frag(ctx, s_txd, nd, s_txpay, s_txpay_len, mss, mtu, pkts + pos0,
+                                        cap_bytes - pos0, off + n0, len + n0, nw, s_txseg,
+                                        s_txseg + max_frames, 0, &used);
+            else if (mss) /* nw entries from nd descriptors */
                 rc = rxg_tx_encode_tso(ctx, s_txd, nd, s_txpay, s_txpay_len, mss, pkts + pos0,
                                        cap_bytes - pos0, off + n0, len + n0, nw, s_txseg,
                                        s_txseg + max_frames, 0, &used);
@@ -4140,6 +4262,19 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
             for (uint32_t k = n0; pos0 && k < n; k++) off[k] += (uint32_t)(pos0 >> 6);
             if (rc == RXG_OK && used != pos - pos0) rc = RXG_ERANGE;
             if (rc == RXG_OK) atomic_fetch_add_explicit(&g_txe_frames, nw, memory_order_relaxed);
+        } else if (nfrag) { /* K2 on the frames that are whole datagrams */
+            uint32_t *xo = malloc((size_t)nw * (sizeof(*xo) + sizeof(uint16_t)));
+            if (!xo) return RXG_ENOMEM;
+            uint16_t *xl = (uint16_t *)(xo + nw);
+            uint32_t m = 0;
+            for (uint32_t k = n0; k < n; k++) {
+                const uint8_t *f = pkts + ((uint64_t)off[k] << 6);
+                if (len[k] >= 34 && f[12] == 0x08 && f[13] == 0x00 && ((f[20] & 0x3F) | f[21]))
+                    continue; /* a fragment: filled by enc_udp_frags */
+                xo[m] = off[k], xl[m] = len[k], m++;
+            }
+            rc = m ? rxg_tx_cksum(ctx, pkts, pos, xo, xl, m, 6) : RXG_OK;
+            free(xo);
         } else {
             rc = rxg_tx_cksum(ctx, pkts, pos, off + n0, len + n0, nw, 6); /* K2 on the GPU */
         }
@@ -4149,7 +4284,8 @@ int nstack_tx_burst(uint8_t *pkts, uint64_t cap_bytes, uint32_t *off, uint16_t *
 }
 
 uint64_t nstack_stat(int which) {
-    if (which < 0 || which > 24) return 0;
+    if (which < 0 || which > 25) return 0;
+    if (which == 25) return (uint64_t)atomic_load_explicit(&g_udp_frags, memory_order_relaxed);
     if (which >= 21) { /* the L2 responder: ARP / echo answers queued, answers dropped for
                           room, echo requests with a bad checksum or a cut capture */
         pthread_mutex_lock(&g_lock);

@@ -324,6 +324,14 @@ _tx_encode_tso = _sig("rxg_tx_encode_tso", _i32, _vp, _vp, _u32, _vp, _u64, _u32
 _tx_encode_tso_host = _sig("rxg_tx_encode_tso_host", _i32, _vp, _u32, _vp, _u64, _u32, _vp, _u64, _u32,
                            _vp, _vp, _u32, _vp, _vp, _u32, C.POINTER(_u64), _vp)
 _tx_tso_count = _sig("rxg_tx_tso_count", _i32, _vp, _u32, _u32, C.POINTER(_u64), C.POINTER(_u64))
+_tx_encode_frag_dev = _sig("rxg_tx_encode_frag_dev", _i32, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _u64,
+                           _u32, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp)
+_tx_encode_frag = _sig("rxg_tx_encode_frag", _i32, _vp, _vp, _u32, _vp, _u64, _u32, _u32, _vp, _u64,
+                       _vp, _vp, _u32, _vp, _vp, _u32, C.POINTER(_u64))
+_tx_encode_frag_host = _sig("rxg_tx_encode_frag_host", _i32, _vp, _u32, _vp, _u64, _u32, _u32, _vp,
+                            _u64, _u32, _vp, _vp, _u32, _vp, _vp, _u32, C.POINTER(_u64), _vp)
+_tx_frag_count = _sig("rxg_tx_frag_count", _i32, _vp, _u32, _u32, _u32, C.POINTER(_u64),
+                      C.POINTER(_u64))
 _tune_txe = _sig("rxg_tune_txe", _i32, _vp, _u32, _u32)
 _rss_split = _sig("rxg_rss_split", _i32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp)
 _rss_split_dev = _sig("rxg_rss_split_dev", _i32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp,
@@ -357,7 +365,8 @@ EXPORTED = ["rxg_open", "rxg_close", "rxg_strerror", "rxg_last_hip_error", "rxg_
             "rxg_pcap_open", "rxg_pcap_close", "rxg_pcap_rewind", "rxg_pcap_read_burst",
             "rxg_pcap_write", "rxg_tx_cksum_dev", "rxg_tx_cksum", "rxg_tx_encode_dev",
             "rxg_tx_encode", "rxg_tx_encode_host", "rxg_tx_encode_tso_dev", "rxg_tx_encode_tso",
-            "rxg_tx_encode_tso_host", "rxg_tx_tso_count", "rxg_tune_txe", "rxg_rss_split",
+            "rxg_tx_encode_tso_host", "rxg_tx_tso_count", "rxg_tx_encode_frag_dev",
+            "rxg_tx_encode_frag", "rxg_tx_encode_frag_host", "rxg_tx_frag_count", "rxg_tune_txe", "rxg_rss_split",
             "rxg_rss_split_dev", "rxg_gather_dev", "rxg_group_id", "rxg_group_open",
             "rxg_group_close", "rxg_group_size", "rxg_counts_allreduce", "rxg_ctx_counts_allreduce",
             "rxg_ddos_dev", "rxg_ddos_bits_dev", "rxg_ddos_window_dev", "rxg_ddos_host",
@@ -935,6 +944,35 @@ class Context:
                                   slot_bytes, p(d_off), p(d_len), out_cap, p(d_first), p(d_nseg),
                                   len_hint, flags, p(d_totals), stream), "rxg_tx_encode_tso_dev")
 
+    def tx_encode_frag(self, txd: np.ndarray, payload: np.ndarray, mss: int, mtu: int,
+                       cap_bytes: int, out_cap: int, flags: int = 0):
+        """tx_encode_tso with UDP datagrams cut at the IPv4 MTU as well:
+        (pkts[:span], off, len, first, nseg, rc)"""
+        txd = np.ascontiguousarray(txd, TXD_DTYPE)
+        payload = np.ascontiguousarray(payload, np.uint8)
+        n = len(txd)
+        pk = np.zeros(max(cap_bytes, 1), np.uint8)
+        off, ln = np.zeros(max(out_cap, 1), np.uint32), np.zeros(max(out_cap, 1), np.uint16)
+        first, nseg = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        span = _u64()
+        rc = _tx_encode_frag(self._h, _ptr(txd), n, _ptr(payload), len(payload), mss, mtu, _ptr(pk),
+                             cap_bytes, _ptr(off), _ptr(ln), out_cap, _ptr(first), _ptr(nseg), flags,
+                             C.byref(span))
+        if rc not in (0, -34):
+            _check(rc, "rxg_tx_encode_frag")
+        return pk[:span.value], off[:out_cap], ln[:out_cap], first[:n], nseg[:n], rc
+
+    def tx_encode_frag_dev(self, d_txd, n: int, d_payload, mss: int, mtu: int, d_pkts,
+                           cap_bytes: int, slot_bytes: int, d_off, d_len, out_cap: int, d_first,
+                           d_nseg, len_hint: int, flags: int, d_totals, stream=None):
+        """tx_encode_tso_dev with UDP datagrams cut at the IPv4 MTU as well (torch
+        tensors or raw ints), asynchronous; d_totals has 8 words"""
+        def p(x):
+            return x if (x is None or isinstance(x, int)) else x.data_ptr()
+        _check(_tx_encode_frag_dev(self._h, p(d_txd), n, p(d_payload), mss, mtu, p(d_pkts), cap_bytes,
+                                   slot_bytes, p(d_off), p(d_len), out_cap, p(d_first), p(d_nseg),
+                                   len_hint, flags, p(d_totals), stream), "rxg_tx_encode_frag_dev")
+
     def process_mbufs(self, mbufs) -> np.ndarray:
         arr = (C.POINTER(Mbuf) * len(mbufs))(*[C.pointer(m) for m in mbufs])
         out = np.zeros(len(mbufs), VERDICT_DTYPE)
@@ -1048,6 +1086,15 @@ def tx_tso_count(txd: np.ndarray, mss: int):
     e, b = _u64(), _u64()
     _check(_tx_tso_count(txd.ctypes.data if len(txd) else None, len(txd), mss, C.byref(e),
                          C.byref(b)), "rxg_tx_tso_count")
+    return e.value, b.value
+
+
+def tx_frag_count(txd: np.ndarray, mss: int, mtu: int):
+    """rxg_tx_frag_count: (entries, packed_bytes) a burst needs at this mss and mtu"""
+    txd = np.ascontiguousarray(txd, TXD_DTYPE)
+    e, b = _u64(), _u64()
+    _check(_tx_frag_count(txd.ctypes.data if len(txd) else None, len(txd), mss, mtu, C.byref(e),
+                          C.byref(b)), "rxg_tx_frag_count")
     return e.value, b.value
 
 
@@ -1239,6 +1286,28 @@ def tx_encode_tso_host(txd: np.ndarray, payload: np.ndarray, mss: int, cap_bytes
     return pk, off[:out_cap], ln[:out_cap], first[:n], nseg[:n], span.value, tot, rc
 
 
+def tx_encode_frag_host(txd: np.ndarray, payload: np.ndarray, mss: int, mtu: int, cap_bytes: int,
+                        out_cap: int, slot_bytes: int = 0, flags: int = 0, fill: int = 0,
+                        fill_entries: int = 0):
+    """rxg_tx_encode_frag_host, tx_encode_tso_host with UDP datagrams cut at the
+    IPv4 MTU as well: (pkts, off, len, first, nseg, span, totals, rc)"""
+    txd = np.ascontiguousarray(txd, TXD_DTYPE)
+    payload = np.ascontiguousarray(payload, np.uint8)
+    n = len(txd)
+    pk = np.full(cap_bytes, fill, np.uint8)
+    off = np.full(max(out_cap, 1), fill_entries & 0xFFFFFFFF, np.uint32)
+    ln = np.full(max(out_cap, 1), fill_entries & 0xFFFF, np.uint16)
+    first, nseg = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+    span, tot = _u64(), np.zeros(8, np.uint32)
+    rc = _tx_encode_frag_host(txd.ctypes.data, n, payload.ctypes.data if len(payload) else None,
+                              len(payload), mss, mtu, pk.ctypes.data, cap_bytes, slot_bytes,
+                              off.ctypes.data, ln.ctypes.data, out_cap, first.ctypes.data,
+                              nseg.ctypes.data, flags, C.byref(span), tot.ctypes.data)
+    if rc not in (0, -34):
+        _check(rc, "rxg_tx_encode_frag_host")
+    return pk, off[:out_cap], ln[:out_cap], first[:n], nseg[:n], span.value, tot, rc
+
+
 def rss_hash(sip: int, dip: int, sport: int, dport: int) -> int:
     return _rss(sip, dip, sport, dport)
 
@@ -1399,6 +1468,7 @@ class NStack:
                    ("nstack_tx_burst", _i32, [_vp, _u64, _vp, _vp, _u32, _i32, _vp]),
                    ("nstack_set_tx_encode", _i32, [_i32]),
                    ("nstack_set_tx_mss", _i32, [_u32]),
+                   ("nstack_set_tx_mtu", _i32, [_u32]),
                    ("nstack_set_rx_gro", _i32, [_u32]),
                    ("nstack_set_rx_order", _i32, [_i32]),
                    ("nstack_set_rx_assemble", _i32, [_i32]),
@@ -1709,6 +1779,12 @@ class NStack:
         """nstack_set_tx_mss: tcp_out sends a fragment longer than mss (a multiple
         of 4; 0 = off) as MSS-sized frames"""
         _check(self.lib.nstack_set_tx_mss(mss), "nstack_set_tx_mss")
+        return 0
+
+    def set_tx_mtu(self, mtu: int):
+        """nstack_set_tx_mtu: udp_out sends a datagram that does not fit the IPv4
+        MTU (68..65535) as IPv4 fragments; 0 = off"""
+        _check(self.lib.nstack_set_tx_mtu(mtu), "nstack_set_tx_mtu")
         return 0
 
     def set_rx_gro(self, window: int):

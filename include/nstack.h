@@ -208,6 +208,27 @@ int nstack_set_tx_encode(int on);
  * segment's frame.  nstack_stat(14) counts the times a fragment went out as
  * more than one frame in a pass.  Returns 0. */
 int nstack_set_tx_mss(uint32_t mss);
+/* IPv4 fragmentation for udp_out's walk.  mtu == 0 (the default): off, a
+ * datagram is one frame of any length up to 65535 bytes.  mtu != 0 (the IPv4
+ * MTU, 68..65535, else RXG_EINVAL; rxg_tx_encode_frag's rule): a datagram
+ * with an ARP entry and 28 + length > mtu goes out as its s fragments
+ * (include/rxgpu.h), all of them or none: it needs s of max_frames and its
+ * fragments' 64-B-rounded bytes of cap_bytes.  If it does not fit what is
+ * left of the pass it stays queued and the pass is full; if it cannot fit
+ * even an empty pass of the caller's size (s > max_frames, or its bytes
+ * exceed cap_bytes) it is dropped and counter 1 counts it, so that it cannot
+ * block its socket for ever.  The 42 + length > 65535 drop applies only to
+ * datagrams that are not cut; the ARP-miss path is unchanged.  The IPv4 id
+ * comes from a per-stack 16-bit counter that starts at 1 after init or fini
+ * and is bumped once per cut datagram, when it is dequeued.  Both framing
+ * paths honour it: the host emits the fragments itself (cksum == 0 leaves
+ * the checksum fields 0), the encoder path (nstack_set_tx_encode) passes one
+ * descriptor per datagram, the id in its seq, to rxg_tx_encode_frag together
+ * with the MSS; frames, off, len, *span, return value and queue state are the
+ * same.  DF is never set, there is no path-MTU discovery, and received
+ * fragments are not reassembled.  nstack_stat(25) counts the datagrams sent as
+ * more than one frame.  nstack_fini resets it.  Returns 0. */
+int nstack_set_tx_mtu(uint32_t mtu);
 
 /* The application side of a benchmark, in one call: every UDP socket read
  * with nrecvfrom until empty, every tcb's receive queue read (nrecv) and its
@@ -440,7 +461,8 @@ int nstack_set_halves(uint32_t min_half);
  * already received, 20 = streams ignored behind a hole
  * (nstack_set_rx_assemble); 21-24 = the L2 responder's ARP answers queued,
  * echo answers queued, answers dropped for room, echo requests with a bad
- * checksum or a cut capture (nstack_set_l2_respond).  Counter 1 also counts TX items dropped (a
+ * checksum or a cut capture (nstack_set_l2_respond); 25 = datagrams sent as
+ * IPv4 fragments (nstack_set_tx_mtu).  Counter 1 also counts TX items dropped (a
  * send ring full, or a datagram too long for a frame). */
 uint64_t nstack_stat(int which);
 

@@ -1072,8 +1072,9 @@ int rxg_tx_encode_host(const rxg_txd *txd, uint32_t n, const uint8_t *payload,
  * FIN (0x01) / PSH (0x08) cleared unless j == s-1; everything else (MACs,
  * addresses, ports, ack, window, urp, hdrlen_off, zero option words) is the
  * descriptor's, both checksums are filled per segment and each frame is
- * zero-filled to its 64-B boundary.  UDP and ARP descriptors are never cut
- * (no IP fragmentation); pay_len 0 gives one segment.  mss == 0: nothing is
+ * zero-filled to its 64-B boundary.  UDP and ARP descriptors are never cut by
+ * this call (rxg_tx_encode_frag_dev below fragments UDP datagrams); pay_len 0
+ * gives one segment.  mss == 0: nothing is
  * cut; mss must be a multiple of 4 (RXG_EINVAL), so that every segment's
  * payload starts 4-B aligned in the payload buffer and lands 2 mod 4 in its
  * frame, the one phase the kernel's funnel knows.
@@ -1128,6 +1129,67 @@ int rxg_tx_encode_tso_host(const rxg_txd *txd, uint32_t n, const uint8_t *payloa
  * skipped for capacity.  Either may be NULL.  RXG_EINVAL for a bad mss. */
 int rxg_tx_tso_count(const rxg_txd *txd, uint32_t n, uint32_t mss, uint64_t *entries,
                      uint64_t *packed_bytes);
+
+/* TX encode with both cuts: TCP segmentation as above and IPv4 fragmentation of
+ * UDP datagrams, in one call, because a burst of nstack_tx_burst mixes both
+ * kinds.  `mss` is rxg_tx_encode_tso_dev's and cuts only RXG_TXD_TCP; `mtu` is
+ * the IPv4 MTU and cuts only RXG_TXD_UDP.  mtu == 0: no datagram is cut; else
+ * 68 <= mtu <= 65535 (RXG_EINVAL).  ARP descriptors and unknown kinds are the
+ * TSO call's.
+ *
+ * A UDP descriptor with mtu != 0: let L = 8 + pay_len, the datagram (UDP
+ * header and payload), and fp = (mtu - 20) & ~7, the datagram bytes per
+ * fragment.
+ *  - 20 + L <= mtu: not cut.  One entry, byte for byte the frame of
+ *    rxg_tx_encode_dev (id 0, fragment field 0) under its skip rules.
+ *  - otherwise s = ceil(L / fp) fragments; fragment j carries datagram bytes
+ *    [j*fp, min((j+1)*fp, L)), b_j of them, in a frame of 34 + b_j bytes.
+ *    s = 0 (skipped: one entry, off = len = 0) when 20 + L > 65535, or when a
+ *    fragment's frame, 34 + min(fp, L), exceeds 65535 bytes or slot_bytes.
+ * Fragment j: the descriptor's Ethernet header; IPv4 0x45, tos 0, total length
+ * 20 + b_j, id = seq & 0xFFFF of the descriptor (big-endian; an uncut
+ * descriptor ignores seq), flags / offset = (j*fp/8) | (j < s-1 ? 0x2000 : 0),
+ * ttl 64, proto 17, its own header checksum (rte_ipv4_cksum as above: the
+ * plain complement), sip, dip; then its datagram bytes.  Bytes 0-7 of the
+ * datagram are {sport, dport, be16(L), checksum}, the checksum
+ * rte_ipv4_udptcp_cksum over the whole datagram with the pseudo-header
+ * (0 -> 0xFFFF): the value rxg_tx_encode_host writes at offset 40 for the
+ * same descriptor uncut, wherever that frame exists.  DF is never set.  With
+ * RXG_TXE_NO_CKSUM every IPv4 and the UDP checksum field stay 0.  Every frame
+ * is zero-filled to its 64-B boundary.
+ *
+ * Everything else is the TSO call's rules 1-5 with "segment" read as
+ * "fragment": entry ownership by max(1, s_k), a descriptor written whole or
+ * not at all, packed frames at 64-B alignment with the first descriptor that
+ * does not fit cap_bytes ending the burst, nothing written at or past
+ * out_cap, bytes outside [slot start, 64-B-rounded frame end) never touched,
+ * d_totals of 8 words.  With mtu == 0 every output equals
+ * rxg_tx_encode_tso_dev's with the same mss (and so, with mss == 0 too,
+ * rxg_tx_encode_dev's).  The payload is read once: each fragment's lane group
+ * leaves the sum of its datagram bytes in a workspace word, and a finish
+ * kernel on the same stream adds a datagram's words and stores the two
+ * checksum bytes into fragment 0.  Receive-side reassembly is not part of
+ * this library (K1 ignores the fragment fields, as the reference does); an
+ * ordinary IP stack reassembles what this writes. */
+int rxg_tx_encode_frag_dev(rxg_ctx *ctx, const rxg_txd *d_txd, uint32_t n, const uint8_t *d_payload,
+                           uint32_t mss, uint32_t mtu, uint8_t *d_pkts, uint64_t cap_bytes,
+                           uint32_t slot_bytes, uint32_t *d_off, uint16_t *d_len, uint32_t out_cap,
+                           uint32_t *d_first, uint32_t *d_nseg, uint32_t len_hint, uint32_t flags,
+                           uint32_t *d_totals, void *stream);
+/* Host form (packed), as rxg_tx_encode_tso; RXG_EINVAL also for a bad mtu. */
+int rxg_tx_encode_frag(rxg_ctx *ctx, const rxg_txd *txd, uint32_t n, const uint8_t *payload,
+                       uint64_t payload_bytes, uint32_t mss, uint32_t mtu, uint8_t *pkts,
+                       uint64_t cap_bytes, uint32_t *off, uint16_t *len, uint32_t out_cap,
+                       uint32_t *first, uint32_t *nseg, uint32_t flags, uint64_t *span);
+/* The same on the CPU (csrc/tx_encode_host.cpp), as rxg_tx_encode_tso_host. */
+int rxg_tx_encode_frag_host(const rxg_txd *txd, uint32_t n, const uint8_t *payload,
+                            uint64_t payload_bytes, uint32_t mss, uint32_t mtu, uint8_t *pkts,
+                            uint64_t cap_bytes, uint32_t slot_bytes, uint32_t *off, uint16_t *len,
+                            uint32_t out_cap, uint32_t *first, uint32_t *nseg, uint32_t flags,
+                            uint64_t *span, uint32_t totals[8]);
+/* rxg_tx_tso_count with both cuts.  RXG_EINVAL for a bad mss or mtu. */
+int rxg_tx_frag_count(const rxg_txd *txd, uint32_t n, uint32_t mss, uint32_t mtu, uint64_t *entries,
+                      uint64_t *packed_bytes);
 
 /* Tuning hook for the TX encode kernel: force entry `variant` of its variant
  * table (csrc/tx_encode.hip k_txe; RXG_TX_AUTO = chosen from len_hint) and cap
