@@ -1,9 +1,10 @@
 // tx_encode_host.cpp — rxg_tx_encode_host: the TX encoder (K5, tx_encode.hip)
 // restated in plain C++ for callers without a GPU and as the tests' reference;
-// rxg_tx_encode_tso_host / rxg_tx_tso_count: the same with TCP payloads cut at
-// an MSS (the TSO layout pass and tx_encode_tso_kernel of tx_encode.hip);
-// rxg_tx_encode_frag_host / rxg_tx_frag_count: the same with UDP datagrams cut
-// at the IPv4 MTU as well, written from the rule in include/rxgpu.h.
+// rxg_tx_encode_frag_host / rxg_tx_frag_count: the same with TCP payloads cut
+// at an MSS and UDP datagrams at the IPv4 MTU (the layout pass with both cuts
+// and tx_encode_frag_kernel of tx_encode.hip), written from the rule in
+// include/rxgpu.h; rxg_tx_encode_tso_host / rxg_tx_tso_count: that with
+// mtu == 0 (the TSO layout pass and tx_encode_tso_kernel).
 // Host only: no HIP, no context.  The frames are those of the reference's
 // encoders with both checksums filled:
 //   ng_encode_udp_apppkt  udp.c:59-98      ng_encode_tcp_apppkt  tcp.c:420-466
@@ -183,7 +184,9 @@ extern "C" int rxg_tx_encode_host(const rxg_txd *txd, uint32_t n, const uint8_t 
     return skipped ? RXG_ERANGE : RXG_OK;
 }
 
-// ---- TCP segmentation (rxg_tx_encode_tso_host, rxg_tx_tso_count) -------------
+// ---- the two cuts: TCP segmentation and IPv4 fragmentation of UDP datagrams ----
+// (rxg_tx_encode_frag_host, rxg_tx_frag_count; rxg_tx_encode_tso_host and
+// rxg_tx_tso_count are the same with mtu == 0, which cuts no datagram)
 namespace {
 
 // how descriptor d is cut: s segments (0 = skipped), the frame length of every
@@ -215,103 +218,6 @@ tso_cut cut_of(const rxg_txd &d, uint32_t mss, uint32_t slot_bytes) {
     c.last = c.s ? (uint32_t)last : 0u;
     return c;
 }
-
-} // namespace
-
-extern "C" int rxg_tx_tso_count(const rxg_txd *txd, uint32_t n, uint32_t mss, uint64_t *entries,
-                                uint64_t *packed_bytes) {
-    if (entries) *entries = 0;
-    if (packed_bytes) *packed_bytes = 0;
-    if (mss & 3u) return RXG_EINVAL;
-    if (n && !txd) return RXG_EINVAL;
-    uint64_t e = 0, u = 0;
-    for (uint32_t k = 0; k < n; ++k) {
-        const tso_cut c = cut_of(txd[k], mss, 0);
-        e += c.s ? c.s : 1;
-        u += c.units();
-    }
-    if (entries) *entries = e;
-    if (packed_bytes) *packed_bytes = u << 6;
-    return RXG_OK;
-}
-
-extern "C" int rxg_tx_encode_tso_host(const rxg_txd *txd, uint32_t n, const uint8_t *payload,
-                                      uint64_t payload_bytes, uint32_t mss, uint8_t *pkts,
-                                      uint64_t cap_bytes, uint32_t slot_bytes, uint32_t *off,
-                                      uint16_t *len, uint32_t out_cap, uint32_t *first,
-                                      uint32_t *nseg, uint32_t flags, uint64_t *span,
-                                      uint32_t totals[8]) {
-    if (span) *span = 0;
-    if (totals) memset(totals, 0, 32);
-    if ((slot_bytes & 63u) || (mss & 3u)) return RXG_EINVAL;
-    if (n == 0) return RXG_OK;
-    if (!txd || !pkts || !first || !nseg || (out_cap && (!off || !len))) return RXG_EINVAL;
-    for (uint32_t k = 0; k < n; ++k) { // every payload inside the payload buffer
-        const tso_cut c = cut_of(txd[k], mss, slot_bytes);
-        if (!c.s || txd[k].kind == RXG_TXD_ARP || !txd[k].pay_len) continue;
-        if (!payload || (uint64_t)txd[k].pay_off16 * 16 + txd[k].pay_len > payload_bytes)
-            return RXG_EINVAL;
-    }
-    const uint64_t lim = 64ull << 32; // offsets are 32 bits of 64-B units
-    const uint64_t cap = cap_bytes < lim ? cap_bytes : lim;
-    uint64_t fe = 0, pos = 0, end = 0, frames = 0;
-    uint32_t written = 0;
-    bool full = false;
-    for (uint32_t k = 0; k < n; ++k) {
-        const rxg_txd &d = txd[k];
-        const tso_cut c = cut_of(d, mss, slot_bytes);
-        const uint64_t ne = c.s ? c.s : 1;
-        bool ok = c.s != 0 && fe + c.s <= out_cap;
-        if (ok && slot_bytes) {
-            ok = (fe + c.s) * slot_bytes <= cap;
-        } else if (ok) {
-            if (full || pos + (c.units() << 6) > cap) ok = false, full = true;
-        }
-        first[k] = fe > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)fe;
-        nseg[k] = ok ? (uint32_t)c.s : 0u;
-        if (!ok) {
-            for (uint64_t e = fe; e < fe + ne && e < out_cap; ++e) off[e] = 0, len[e] = 0;
-            fe += ne;
-            continue;
-        }
-        const uint8_t *src = payload ? payload + (uint64_t)d.pay_off16 * 16 : nullptr;
-        for (uint64_t j = 0; j < c.s; ++j) {
-            const uint32_t fl = j + 1 == c.s ? c.last : c.full;
-            const uint64_t at = slot_bytes ? (fe + j) * slot_bytes : pos;
-            rxg_txd g = d;
-            if (c.s > 1) { // (s == 1: the descriptor as it is, whatever mss)
-                g.seq = d.seq + (uint32_t)(j * mss);
-                g.pay_len = fl - c.hdr;
-                if (j + 1 != c.s) g.tcp_flags = d.tcp_flags & (uint8_t)~0x09u; // FIN, PSH
-            }
-            uint8_t *m = pkts + at;
-            encode(m, g, fl, src ? src + j * mss : nullptr);
-            if (d.kind != RXG_TXD_ARP && !(flags & RXG_TXE_NO_CKSUM))
-                fill_cksums(m, fl, d.kind == RXG_TXD_TCP);
-            memset(m + fl, 0, align64(fl) - fl);
-            off[fe + j] = (uint32_t)(at >> 6);
-            len[fe + j] = (uint16_t)fl;
-            end = at + align64(fl);
-            if (slot_bytes == 0) pos = end;
-        }
-        frames += c.s;
-        fe += ne;
-        ++written;
-    }
-    if (span) *span = end;
-    if (totals) {
-        totals[0] = (uint32_t)frames;
-        totals[1] = (uint32_t)end;
-        totals[2] = (uint32_t)(end >> 32);
-        totals[3] = n - written;
-        totals[4] = (uint32_t)fe;
-        totals[5] = (uint32_t)(fe >> 32);
-    }
-    return written != n ? RXG_ERANGE : RXG_OK;
-}
-
-// ---- IPv4 fragmentation of UDP datagrams (rxg_tx_encode_frag_host, rxg_tx_frag_count)
-namespace {
 
 // cut_of with the second cut: a UDP descriptor whose datagram (L = 8 + pay_len
 // bytes) does not fit the IPv4 MTU becomes s fragments of fp = (mtu - 20) & ~7
@@ -493,4 +399,20 @@ extern "C" int rxg_tx_encode_frag_host(const rxg_txd *txd, uint32_t n, const uin
         totals[5] = (uint32_t)(fe >> 32);
     }
     return written != n ? RXG_ERANGE : RXG_OK;
+}
+
+// ---- TCP segmentation alone: mtu == 0 (the checks above are these calls' own)
+extern "C" int rxg_tx_tso_count(const rxg_txd *txd, uint32_t n, uint32_t mss, uint64_t *entries,
+                                uint64_t *packed_bytes) {
+    return rxg_tx_frag_count(txd, n, mss, 0, entries, packed_bytes);
+}
+
+extern "C" int rxg_tx_encode_tso_host(const rxg_txd *txd, uint32_t n, const uint8_t *payload,
+                                      uint64_t payload_bytes, uint32_t mss, uint8_t *pkts,
+                                      uint64_t cap_bytes, uint32_t slot_bytes, uint32_t *off,
+                                      uint16_t *len, uint32_t out_cap, uint32_t *first,
+                                      uint32_t *nseg, uint32_t flags, uint64_t *span,
+                                      uint32_t totals[8]) {
+    return rxg_tx_encode_frag_host(txd, n, payload, payload_bytes, mss, 0, pkts, cap_bytes, slot_bytes,
+                                   off, len, out_cap, first, nseg, flags, span, totals);
 }
