@@ -2128,23 +2128,21 @@ static int deliver_burst(rxg_mbuf *const *m, uint32_t n, const rxg_verdict *v, i
     return delivered;
 }
 
-static void deliver_tcp_sorted(const rxg_segment *sg, uint32_t nseg, const rxg_tcp_run *run,
-                               uint32_t nrun, const struct asm_view *av, const uint8_t *payload,
-                               int32_t pl_ref, rxg_mbuf *const *m, uint8_t *handled, int *rc_out);
-static uint32_t host_segments(rxg_mbuf *const *m, uint32_t n, const rxg_verdict *v,
-                              rxg_segment *sg);
-static int deliver_udp_batches(rxg_mbuf *const *m, const rxg_dgram *dg, const uint32_t *first,
-                               const uint8_t *payload, uint32_t nf);
+/* the bytes of a datagram's len payload bytes the frame's capture holds
+ * (min(dgram_len - 8, caplen - 42)) */
+static inline uint32_t dgram_captured(const rxg_mbuf *mb, uint32_t len) {
+    const uint32_t avail = mb->data_len > 42u ? mb->data_len - 42u : 0u;
+    return len < avail ? len : avail;
+}
 
 /* The datagram records of a burst whose verdicts came from elsewhere
  * (nstack_deliver), as the GPU's compaction hands them to nstack_rx_burst
  * (rxg_udp_compact_dev): the rc-0 UDP verdicts naming a live socket id,
  * grouped by id in burst order (first[f] .. first[f + 1]), each captured
- * payload (min(dgram_len - 8, caplen - 42) bytes) at a 16-B aligned offset of
- * one buffer, a socket's payloads contiguous.  So the host-only path delivers
- * UDP through the same batches.  Returns the datagrams (0: none, or out of
- * memory: the frame-by-frame path then delivers them); *payload is the
- * buffer to free. */
+ * payload (dgram_captured) at a 16-B aligned offset of one buffer, a socket's
+ * payloads contiguous.  So the host-only path delivers UDP through the same
+ * batches.  Returns the datagrams (0: none, or out of memory: the
+ * frame-by-frame path then delivers them); *payload is the buffer to free. */
 static uint32_t host_dgrams(rxg_mbuf *const *m, uint32_t n, const rxg_verdict *v, uint32_t nf,
                             rxg_dgram **dg_out, uint32_t **first_out, uint8_t **payload) {
     *dg_out = NULL, *first_out = NULL, *payload = NULL;
@@ -2174,8 +2172,7 @@ static uint32_t host_dgrams(rxg_mbuf *const *m, uint32_t n, const rxg_verdict *v
         d->sip = cap >= 30 ? rd32(f + 26) : 0;
         d->sport = cap >= 36 ? rd16(f + 34) : 0;
         d->len = (uint16_t)v[i].payload_len;
-        const uint32_t avail = cap > 42u ? cap - 42u : 0u;
-        bytes += ((d->len < avail ? d->len : avail) + 15u) & ~15u;
+        bytes += (dgram_captured(m[i], d->len) + 15u) & ~15u;
     }
     free(pos);
     uint8_t *pl = malloc(bytes + 16);
@@ -2187,116 +2184,13 @@ static uint32_t host_dgrams(rxg_mbuf *const *m, uint32_t n, const rxg_verdict *v
     for (uint32_t j = 0; j < nd; j++) { /* socket by socket: each one's payloads contiguous */
         rxg_dgram *d = &dg[j];
         const rxg_mbuf *mb = m[d->frame];
-        const uint32_t avail = mb->data_len > 42u ? mb->data_len - 42u : 0u;
-        const uint32_t c = d->len < avail ? d->len : avail;
+        const uint32_t c = dgram_captured(mb, d->len);
         d->offset = off;
         memcpy(pl + off, (const uint8_t *)mb->buf_addr + mb->data_off + 42u, c);
         off += (c + 15u) & ~15u;
     }
     *dg_out = dg, *first_out = first, *payload = pl;
     return nd;
-}
-
-int nstack_deliver(rxg_mbuf *const *m, uint32_t n, const rxg_verdict *v, uint64_t gen,
-                   int *rc_out) {
-    if (!m || !v) return n ? RXG_EINVAL : 0;
-    reclaim();
-    pthread_mutex_lock(&g_lock);
-    /* (refused while pipelined bursts are pending: their frames come first) */
-    int rc = g_ctx && !g_pend_n ? RXG_OK : RXG_EINVAL;
-    int delivered = 0;
-    if (rc == RXG_OK) {
-        g_burst_stale = gen != g_snap_gen; /* classified against other lists */
-        g_burst_mutated = 0;
-        g_ck_on = ck_active(); /* (the alarm as it stood before this burst) */
-        g_ck_st = NULL;
-        if (g_ck_on) {
-            g_ck_p.t = ck_now();
-            if (!g_burst_stale && n) ck_host_burst(m, n, v);
-        }
-        if (g_ddos && n) ddos_host_burst(m, n); /* (sees the frames; changes nothing below) */
-        if (g_l2 && n) l2_host_frames(m, n, v);  /* (the rule reads cls alone: stale or not) */
-        const uint8_t *done = NULL;
-        rxg_dgram *dg = NULL;
-        uint32_t *first = NULL;
-        uint8_t *pl = NULL;
-        if (!g_burst_stale && n && host_dgrams(m, n, v, s_udp_cap, &dg, &first, &pl)) {
-            delivered += deliver_udp_batches(m, dg, first, pl, s_udp_cap);
-            g_udp_done = 1; /* the per-frame loop leaves UDP alone */
-        }
-        free(dg), free(first), free(pl);
-        if (!g_burst_stale && n) { /* the verdicts' flow ids name the live blocks */
-            rxg_segment *sg = malloc((size_t)n * sizeof(*sg));
-            if (!grow((void **)&s_handled, &s_handled_cap, n, 1) && sg) {
-                memset(s_handled, 0, n);
-                const uint32_t k = host_segments(m, n, v, sg);
-                /* ordering and coalescing: the permutation and the runs by the
-                 * rules' host restatements, the source addresses read from the
-                 * mbufs (out of memory: arrival order, the segments one by one) */
-                rxg_tcp_run *run = NULL;
-                uint32_t nrun = 0;
-                uint32_t *sip =
-                    (g_gro || g_order || g_assemble) && k ? malloc((size_t)k * sizeof(*sip)) : NULL;
-                if (sip)
-                    for (uint32_t j = 0; j < k; j++) {
-                        const rxg_mbuf *mb = m[sg[j].frame];
-                        const uint8_t *f = (const uint8_t *)mb->buf_addr + mb->data_off;
-                        sip[j] = 0;
-                        for (uint32_t q = 0; q < 4; q++)
-                            if (26u + q < mb->data_len) sip[j] |= (uint32_t)f[26u + q] << (8u * q);
-                    }
-                if (sip && (g_order || g_assemble)) { /* (assembly implies ordering) */
-                    uint32_t *perm = malloc((size_t)k * sizeof(*perm)), moved = 0;
-                    rxg_segment *so = malloc((size_t)k * sizeof(*so));
-                    uint32_t *sipo = malloc((size_t)k * sizeof(*sipo));
-                    if (perm && so && sipo &&
-                        rxg_tcp_order_host(sg, sip, k, perm, &moved) == RXG_OK && moved) {
-                        for (uint32_t j = 0; j < k; j++) so[j] = sg[perm[j]], sipo[j] = sip[perm[j]];
-                        memcpy(sg, so, (size_t)k * sizeof(*sg));
-                        memcpy(sip, sipo, (size_t)k * sizeof(*sip));
-                        g_order_moved += moved;
-                    }
-                    free(perm), free(so), free(sipo);
-                }
-                if (sip && g_gro) run = malloc((size_t)k * sizeof(*run));
-                if (run && rxg_tcp_runs_host(sg, sip, k, g_gro, run, &nrun) != RXG_OK) nrun = 0;
-                /* assembly: the streams by the rule's host restatement on the
-                 * ordered records, which then carry ncopy = take as the device's do
-                 * (out of memory: every TCP frame takes the frame-by-frame path,
-                 * which validates it on its own) */
-                struct asm_view av = {NULL, 0};
-                rxg_tcp_stream *stm = NULL;
-                if (g_assemble && k) {
-                    uint32_t *w = sip ? malloc((size_t)k * 4 * sizeof(*w)) : NULL, nst = 0;
-                    stm = w ? malloc((size_t)k * sizeof(*stm)) : NULL;
-                    if (stm) {
-                        for (uint32_t j = 0; j < k; j++) {
-                            const uint32_t cap = m[sg[j].frame]->data_len, from = 34u + 4u * sg[j].hl;
-                            w[j] = cap > from ? cap - from : 0u;
-                        }
-                        if (rxg_tcp_assemble_host(sg, sip, w, k, stm, &nst, w + k, w + 2 * k,
-                                                  w + 3 * k) == RXG_OK) {
-                            for (uint32_t j = 0; j < k; j++) sg[j].ncopy = (uint16_t)w[2 * k + j];
-                            av.st = stm, av.n = nst;
-                        }
-                    }
-                    free(w);
-                }
-                if (!g_assemble || av.st)
-                    deliver_tcp_sorted(sg, k, nrun ? run : NULL, nrun, av.st ? &av : NULL, NULL, -1, m,
-                                       s_handled, rc_out);
-                free(sip), free(run), free(stm);
-                done = s_handled;
-            }
-            free(sg);
-        }
-        delivered += deliver_burst(m, n, v, rc_out, done);
-        g_udp_done = 0;
-        g_ck_on = 0, g_ck_st = NULL;
-        atomic_fetch_add_explicit(&g_deliveries, 1, memory_order_release);
-    }
-    pthread_mutex_unlock(&g_lock);
-    return rc == RXG_OK ? delivered : rc;
 }
 
 /* UDP delivery of a whole burst from the GPU's compaction (g_lock held):
@@ -2320,11 +2214,8 @@ static int deliver_udp_batches(rxg_mbuf *const *m, const rxg_dgram *dg, const ui
             continue;
         }
         const rxg_dgram *d0 = &dg[a], *dl = &dg[a + take - 1];
-        const uint32_t lastc = (uint32_t)dl->len < (m[dl->frame]->data_len > 42u
-                                                        ? m[dl->frame]->data_len - 42u : 0u)
-                                   ? dl->len : (m[dl->frame]->data_len > 42u
-                                                    ? m[dl->frame]->data_len - 42u : 0u);
-        const size_t bytes = (size_t)(dl->offset - d0->offset) + lastc;
+        const size_t bytes =
+            (size_t)(dl->offset - d0->offset) + dgram_captured(m[dl->frame], dl->len);
         struct offload *o = bp_alloc(sizeof(*o) + sizeof(struct dgram_batch) +
                                      take * sizeof(struct dgram_meta) + bytes + 1);
         if (!o) {
@@ -2341,12 +2232,10 @@ static int deliver_udp_batches(rxg_mbuf *const *m, const rxg_dgram *dg, const ui
         memcpy(b->data, payload + d0->offset, bytes); /* the socket's slice, once */
         for (uint32_t j = 0; j < take; j++) {
             const rxg_dgram *d = &dg[a + j];
-            const uint32_t cap = m[d->frame]->data_len;
-            const uint32_t avail = cap > 42u ? cap - 42u : 0u;
             b->meta[j].sip = d->sip;
             b->meta[j].sport = d->sport;
             b->meta[j].len = d->len;
-            b->meta[j].ncopy = (uint16_t)(d->len < avail ? d->len : avail);
+            b->meta[j].ncopy = (uint16_t)dgram_captured(m[d->frame], d->len);
             b->meta[j].off = d->offset - d0->offset;
         }
         o->batch = b;
@@ -2365,7 +2254,8 @@ static int deliver_udp_batches(rxg_mbuf *const *m, const rxg_dgram *dg, const ui
     return delivered;
 }
 
-/* A connection's segments of one burst, from the GPU's segment sort, through
+/* ---- TCP delivery of a burst, connection by connection ---------------------
+ * A connection's segments of one burst, from the GPU's segment sort, through
  * tcp_handle_established (tcp.c:218-297) in burst order (g_lock held).  Only
  * for a tcb whose state cannot move a lookup: ESTABLISHED (it may go to
  * CLOSE_WAIT on a FIN, which no lookup reads) and the states whose segments
@@ -2375,201 +2265,67 @@ static int deliver_udp_batches(rxg_mbuf *const *m, const rxg_dgram *dg, const ui
  * by connection equals the reference's frame-by-frame loop.  The receive
  * fragments the segments queue (ng_tcp_enqueue_recvbuffer, tcp.c:133-185)
  * and the ACKs they send (tcp.c:187-216) go in as one batch item each: one
- * allocation.  With a held payload buffer (pl_ref >= 0) a fragment whose
- * payload was captured whole points straight into it (no copy: the batch
- * holds the buffer until it is freed); otherwise the payload is copied, zero
- * filled past the capture.  Returns 0, or 1 when the tcb's state needs the
- * frame-by-frame path (LISTEN, SYN_RCVD, LAST_ACK).
- * Receive coalescing (run non-NULL: the connection's nr runs, run[].first
- * counted from sg - base): a run of more than one segment — in-sequence
- * PSH|ACK segments with equal ack, payloads captured whole and byte-contiguous
- * at the run's offset — makes one fragment of the run's bytes (pointing into
- * the held buffer, else copied) and one ACK, whose acknum is rcv_nxt after the
- * run: the ACK that closes the run in the segment-by-segment order.  A run of
- * one takes the segment's path.  A full receive ring drops whole runs.
- * Connections on the frame-by-frame path are never coalesced. */
-static int deliver_tcp_conn(struct tcp_stream *s, const rxg_segment *sg, uint32_t k,
-                            const rxg_tcp_run *run, uint32_t nr, uint32_t base,
-                            const uint8_t *payload, int32_t pl_ref, rxg_mbuf *const *m,
-                            uint8_t *handled, int *rc_out) {
+ * allocation.  Both connection functions below work in the same four steps:
+ * count what the records make, open the pair of batches (conn_open), walk the
+ * records writing fragments (put_frag) and ACKs (put_ack), close (conn_close).
+ * The steps are always inlined (CONN_STEP), as the hand-written copies they
+ * replace were: at 4 segments per connection a call per step shows in phase 7,
+ * and put_frag out of line cost in-place delivery 5 %
+ * (profiles/nstack_deliver_refactor/sock_ab.txt). */
+#define CONN_STEP static inline __attribute__((always_inline))
+struct conn_batch {
+    struct frag_batch *rb, *ab; /* receive fragments, ACKs (NULL: no room, or out of memory) */
+    uint32_t rtake, atake;      /* the fragments the rings have room for */
+    unsigned char *pp;          /* where the next copied payload goes in rb's block */
+    uint32_t fi, ai;            /* fragments / ACKs made so far (those past the room too) */
+};
+
+/* The connection takes its k records (marked in handled, rc 0, stat 2), or
+ * returns 1: its state needs the frame-by-frame path (LISTEN, SYN_RCVD,
+ * LAST_ACK: tcp_dispatch validates each frame there) */
+CONN_STEP int conn_claim(const struct tcp_stream *s, const rxg_segment *sg, uint32_t k,
+                      uint8_t *handled, int *rc_out) {
     if (s->status == TCP_STATUS_LISTEN || s->status == TCP_STATUS_SYN_RCVD ||
         s->status == TCP_STATUS_LAST_ACK)
         return 1;
-    /* the fragments and ACKs the segments make, in order (the state changes
-     * at most once: ESTABLISHED -> CLOSE_WAIT on a FIN) */
-    uint32_t nfr = 0, nack = 0;
-    uint64_t pbytes = 0;
-    int st = s->status;
-    const int inpl = g_inplace; /* payloads captured whole stay in their frames */
-    uint32_t ri = 0; /* the run that holds segment j */
     for (uint32_t j = 0; j < k; j++) {
         handled[sg[j].frame] = 1;
         if (rc_out) rc_out[sg[j].frame] = RXG_RC_OK;
-        if (st != TCP_STATUS_ESTABLISHED) continue;
-        if (run) {
-            while (ri + 1 < nr && run[ri + 1].first - base <= j) ri++;
-            if (run[ri].nseg > 1) { /* one fragment, one ACK for the run */
-                if (run[ri].first - base == j) {
-                    nfr++, nack++;
-                    if (pl_ref < 0) pbytes += run[ri].bytes; /* (copied) */
-                    g_gro_absorbed += run[ri].nseg - 1;
-                }
-                continue;
-            }
-        }
-        if (sg[j].flags & TCP_PSH) {
-            nfr++, nack++;
-            if (sg[j].plen > 0 && sg[j].ncopy != (uint32_t)sg[j].plen) /* cut short: copied */
-                pbytes += (uint64_t)sg[j].plen;
-            else if (sg[j].plen > 0 && !inpl && pl_ref < 0)
-                pbytes += (uint64_t)sg[j].plen; /* (copied) */
-        }
-        if (sg[j].flags & TCP_FIN) nfr++, nack++, st = TCP_STATUS_CLOSE_WAIT;
     }
     g_stat[2] += k;
-    if (!nfr) return 0;
+    return 0;
+}
+
+CONN_STEP struct frag_batch *frag_batch_new(uint32_t n, uint64_t extra) {
+    struct frag_batch *b = bp_alloc(sizeof(*b) + n * sizeof(struct tcp_fragment) + extra);
+    if (!b) return NULL;
+    memset(&b->item, 0, sizeof(b->item));
+    b->item.batch = b;
+    b->n = n;
+    b->next = 0;
+    b->frag = (struct tcp_fragment *)(b + 1);
+    b->pl_ref = -1;
+    return b;
+}
+
+/* s->mutex taken (conn_close lets it go); room for nfr fragments with pbytes
+ * of copied payload and nack ACKs: only those that fit (a full ring drops the
+ * rest, as successive enqueues would) */
+CONN_STEP void conn_open(struct conn_batch *cb, struct tcp_stream *s, uint32_t nfr, uint32_t nack,
+                      uint64_t pbytes) {
     pthread_mutex_lock(&s->mutex);
     const uint32_t rroom = s->rq < D_RING_SIZE ? D_RING_SIZE - s->rq : 0;
     const uint32_t aroom = s->sq < D_RING_SIZE ? D_RING_SIZE - s->sq : 0;
-    const uint32_t rtake = nfr < rroom ? nfr : rroom, atake = nack < aroom ? nack : aroom;
-    struct frag_batch *rb = NULL, *ab = NULL;
-    if (rtake) { /* payload room: only the fragments that fit (a full ring drops the rest) */
-        rb = bp_alloc(sizeof(*rb) + rtake * sizeof(struct tcp_fragment) + pbytes + 1);
-        if (rb) {
-            memset(&rb->item, 0, sizeof(rb->item));
-            rb->item.batch = rb;
-            rb->n = rtake;
-            rb->next = 0;
-            rb->frag = (struct tcp_fragment *)(rb + 1);
-            rb->pl_ref = -1;
-        }
-    }
-    if (atake) {
-        ab = bp_alloc(sizeof(*ab) + atake * sizeof(struct tcp_fragment));
-        if (ab) {
-            memset(&ab->item, 0, sizeof(ab->item));
-            ab->item.batch = ab;
-            ab->n = atake;
-            ab->next = 0;
-            ab->frag = (struct tcp_fragment *)(ab + 1);
-            ab->pl_ref = -1;
-        }
-    }
-    unsigned char *pp = rb ? (unsigned char *)(rb->frag + rtake) : NULL;
-    uint32_t fi = 0, ai = 0;
-    /* one receive fragment (tcp.c:133-185): plen > 0 a payload copy (bytes past
-     * the capture read 0), else the 0-length EOF; g_stat as tcp_enqueue_rcv */
-    #define PUT_FRAG(SEG, PLEN)                                                              \
-        do {                                                                                 \
-            if (fi < rtake && rb) {                                                          \
-                struct tcp_fragment *fr = &rb->frag[fi];                                     \
-                memset(fr, 0, sizeof(*fr));                                                  \
-                fr->dport = ntohs((SEG)->dport);                                             \
-                fr->sport = ntohs((SEG)->sport);                                             \
-                if ((PLEN) > 0 && inpl && (SEG)->ncopy == (uint32_t)(PLEN)) {                \
-                    rxg_mbuf *mb_ = m[(SEG)->frame]; /* in its frame, the mbuf held */       \
-                    fr->data = (unsigned char *)mb_->buf_addr + mb_->data_off + 34u +        \
-                               4u * (SEG)->hl;                                               \
-                    fr->length = (uint32_t)(PLEN);                                           \
-                    fr->mb = mb_;                                                            \
-                    mb_get(mb_);                                                             \
-                } else if ((PLEN) > 0 && pl_ref >= 0 && (SEG)->ncopy == (uint32_t)(PLEN)) {  \
-                    fr->data = (unsigned char *)payload + (SEG)->offset; /* (no copy) */     \
-                    fr->length = (uint32_t)(PLEN);                                           \
-                    rb->pl_ref = pl_ref;                                                     \
-                } else if ((PLEN) > 0) {                                                     \
-                    fr->data = pp;                                                           \
-                    fr->length = (uint32_t)(PLEN);                                           \
-                    memcpy(pp, payload ? payload + (SEG)->offset                             \
-                                       : (const uint8_t *)m[(SEG)->frame]->buf_addr +        \
-                                             m[(SEG)->frame]->data_off + 34u + 4u * (SEG)->hl, \
-                           (SEG)->ncopy);                                                    \
-                    if ((uint32_t)(PLEN) > (SEG)->ncopy)                                     \
-                        memset(pp + (SEG)->ncopy, 0, (uint32_t)(PLEN) - (SEG)->ncopy);       \
-                    pp += (uint32_t)(PLEN);                                                  \
-                    g_copied_bytes += (uint32_t)(PLEN);                                      \
-                }                                                                            \
-                g_stat[4]++;                                                                 \
-            } else {                                                                         \
-                g_stat[1]++;                                                                 \
-            }                                                                                \
-            fi++;                                                                            \
-        } while (0)
-    /* the ACK after it (ng_tcp_send_ackpkt, tcp.c:187-216) */
-    #define PUT_ACK(SEG)                                                                     \
-        do {                                                                                 \
-            if (ai < atake && ab) {                                                          \
-                struct tcp_fragment *a = &ab->frag[ai];                                      \
-                memset(a, 0, sizeof(*a));                                                    \
-                a->sport = (SEG)->dport;                                                     \
-                a->dport = (SEG)->sport;                                                     \
-                a->seqnum = s->snd_nxt;                                                      \
-                a->acknum = s->rcv_nxt;                                                      \
-                a->tcp_flags = TCP_ACK;                                                      \
-                a->windows = D_TCP_INITIAL_WINDOW;                                           \
-                a->hdrlen_off = 0x50;                                                        \
-            }                                                                                \
-            ai++;                                                                            \
-        } while (0)
-    ri = 0;
-    for (uint32_t j = 0; j < k && s->status == TCP_STATUS_ESTABLISHED; j++) {
-        const rxg_segment *g = &sg[j];
-        if (run) {
-            while (ri + 1 < nr && run[ri + 1].first - base <= j) ri++;
-            if (run[ri].nseg > 1) { /* (j is the run's first segment) */
-                const rxg_tcp_run *r = &run[ri];
-                if (fi < rtake && rb) {
-                    struct tcp_fragment *fr = &rb->frag[fi];
-                    memset(fr, 0, sizeof(*fr));
-                    fr->dport = ntohs(g->dport);
-                    fr->sport = ntohs(g->sport);
-                    fr->length = r->bytes;
-                    if (pl_ref >= 0) {
-                        fr->data = (unsigned char *)payload + r->offset; /* (no copy) */
-                        rb->pl_ref = pl_ref;
-                    } else {
-                        fr->data = pp;
-                        if (payload) {
-                            memcpy(pp, payload + r->offset, r->bytes);
-                            pp += r->bytes;
-                        } else { /* (host verdicts: from the frames) */
-                            for (uint32_t q = 0; q < r->nseg; q++) {
-                                const rxg_mbuf *mb_ = m[g[q].frame];
-                                memcpy(pp, (const uint8_t *)mb_->buf_addr + mb_->data_off + 34u +
-                                               4u * g[q].hl, g[q].ncopy);
-                                pp += g[q].ncopy;
-                            }
-                        }
-                        g_copied_bytes += r->bytes;
-                    }
-                    g_stat[4]++;
-                } else {
-                    g_stat[1]++;
-                }
-                fi++;
-                s->rcv_nxt += r->bytes;
-                s->snd_nxt = g->ack;
-                PUT_ACK(g);
-                j += r->nseg - 1;
-                continue;
-            }
-        }
-        if (g->flags & TCP_PSH) { /* tcp.c:226-262 */
-            PUT_FRAG(g, g->plen);
-            s->rcv_nxt += (uint32_t)g->plen;
-            s->snd_nxt = g->ack;
-            PUT_ACK(g);
-        }
-        if (g->flags & TCP_FIN) { /* tcp.c:264-294: CLOSE_WAIT, EOF, ACK */
-            s->status = TCP_STATUS_CLOSE_WAIT;
-            PUT_FRAG(g, 0);
-            s->rcv_nxt += 1;
-            s->snd_nxt = g->ack;
-            PUT_ACK(g);
-        }
-    }
-    #undef PUT_FRAG
-    #undef PUT_ACK
+    cb->rtake = nfr < rroom ? nfr : rroom, cb->atake = nack < aroom ? nack : aroom;
+    cb->rb = cb->rtake ? frag_batch_new(cb->rtake, pbytes + 1) : NULL;
+    cb->ab = cb->atake ? frag_batch_new(cb->atake, 0) : NULL;
+    cb->pp = cb->rb ? (unsigned char *)(cb->rb->frag + cb->rtake) : NULL;
+    cb->fi = cb->ai = 0;
+}
+
+/* the two batches onto the tcb's rings, the reader woken, s->mutex let go */
+CONN_STEP void conn_close(struct conn_batch *cb, struct tcp_stream *s) {
+    struct frag_batch *rb = cb->rb, *ab = cb->ab;
     if (rb) {
         if (rb->pl_ref >= 0) { /* until the batch is freed */
             rxg_payload_hold(g_ctx, rb->pl_ref);
@@ -2578,9 +2334,9 @@ static int deliver_tcp_conn(struct tcp_stream *s, const rxg_segment *sg, uint32_
         }
         if (ring_enqueue(s->rcvbuf, &rb->item)) { /* (not reached: items <= fragments <= capacity) */
             frag_item_free(&rb->item);
-            g_stat[4] -= rtake, g_stat[1] += rtake;
+            g_stat[4] -= cb->rtake, g_stat[1] += cb->rtake;
         } else {
-            cnt_set(&s->rq, s->rq + rtake);
+            cnt_set(&s->rq, s->rq + cb->rtake);
             pthread_cond_signal(&s->cond); /* tcp.c:178-180 */
         }
     }
@@ -2588,35 +2344,191 @@ static int deliver_tcp_conn(struct tcp_stream *s, const rxg_segment *sg, uint32_
         if (ring_enqueue(s->sndbuf, &ab->item))
             bp_free(ab);
         else
-            cnt_set(&s->sq, s->sq + atake);
+            cnt_set(&s->sq, s->sq + cb->atake);
     }
     pthread_mutex_unlock(&s->mutex);
+}
+
+/* a segment's payload in its frame */
+static inline unsigned char *seg_payload(rxg_mbuf *const *m, const rxg_segment *g) {
+    const rxg_mbuf *mb = m[g->frame];
+    return (unsigned char *)mb->buf_addr + mb->data_off + 34u + 4u * g->hl;
+}
+
+/* The bytes of one receive fragment: `length` of them (0: the 0-length EOF
+ * fragment), the first ncopy captured (what is past them reads 0), carried by
+ * the records g[0..nseg) — in their frames, and from `offset` of the burst's
+ * payload buffer when the library gathered one.  tail: each record holds the
+ * last ncopy bytes of its payload (assembly: ncopy = take) and the fragment
+ * starts `skip` bytes into them; otherwise the first ncopy, skip = 0. */
+struct frag_src {
+    const rxg_segment *g;
+    uint32_t nseg, offset, length, ncopy, skip;
+    int tail;
+};
+
+/* One receive fragment (tcp.c:133-185), ports from x->g; g_stat as
+ * tcp_enqueue_rcv (4: queued, 1: no room).  Bytes captured whole stay where
+ * they are — in the frame with its mbuf held (inpl; one record), or in the
+ * held pooled buffer pl_ref — and the batch keeps them until it is freed;
+ * otherwise they are copied into the batch's block, from the payload buffer
+ * or (host verdicts: payload NULL) gathered from the frames, zero filled past
+ * the capture.  Each caller's constants (one record, no in-place, the EOF's
+ * length 0) leave it the branches that caller can take. */
+CONN_STEP void put_frag(struct conn_batch *cb, const struct frag_src *x, const uint8_t *payload,
+                        int32_t pl_ref, rxg_mbuf *const *m, int inpl) {
+    if (cb->fi++ >= cb->rtake || !cb->rb) {
+        g_stat[1]++;
+        return;
+    }
+    struct tcp_fragment *fr = &cb->rb->frag[cb->fi - 1];
+    memset(fr, 0, sizeof(*fr));
+    fr->dport = ntohs(x->g->dport);
+    fr->sport = ntohs(x->g->sport);
+    fr->length = x->length;
+    g_stat[4]++;
+    if (!x->length) return; /* (nrecv's EOF) */
+    const int whole = x->ncopy == x->length;
+    if (whole && inpl) {
+        fr->data = seg_payload(m, x->g);
+        fr->mb = m[x->g->frame];
+        mb_get(fr->mb);
+    } else if (whole && pl_ref >= 0) {
+        fr->data = (unsigned char *)payload + x->offset;
+        cb->rb->pl_ref = pl_ref;
+    } else {
+        fr->data = cb->pp;
+        if (payload) {
+            memcpy(cb->pp, payload + x->offset, x->ncopy);
+        } else {
+            uint32_t pos = 0; /* of record j's bytes among the records' */
+            for (uint32_t j = 0; j < x->nseg; j++) {
+                const rxg_segment *g = &x->g[j];
+                const uint32_t t = g->ncopy, lo = pos > x->skip ? pos : x->skip;
+                if (pos + t > lo)
+                    memcpy(cb->pp + (lo - x->skip),
+                           seg_payload(m, g) + (x->tail ? (uint32_t)g->plen - t : 0u) + (lo - pos),
+                           pos + t - lo);
+                pos += t;
+            }
+        }
+        if (x->length > x->ncopy) memset(cb->pp + x->ncopy, 0, x->length - x->ncopy);
+        cb->pp += x->length;
+        g_copied_bytes += x->length;
+    }
+}
+
+/* the ACK behind it (ng_tcp_send_ackpkt, tcp.c:187-216), after rcv_nxt and
+ * snd_nxt have moved; ports from g */
+CONN_STEP void put_ack(struct conn_batch *cb, const struct tcp_stream *s, const rxg_segment *g) {
+    if (cb->ai++ >= cb->atake || !cb->ab) return;
+    struct tcp_fragment *a = &cb->ab->frag[cb->ai - 1];
+    memset(a, 0, sizeof(*a));
+    a->sport = g->dport;
+    a->dport = g->sport;
+    a->seqnum = s->snd_nxt;
+    a->acknum = s->rcv_nxt;
+    a->tcp_flags = TCP_ACK;
+    a->windows = D_TCP_INITIAL_WINDOW;
+    a->hdrlen_off = 0x50;
+}
+
+/* The segment form: every PSH segment makes a fragment (payload captured
+ * whole: in place or in the held buffer, else copied) and an ACK, a FIN the
+ * EOF fragment and an ACK.  Returns 0, or 1 for the frame-by-frame path.
+ * Receive coalescing (run non-NULL: the connection's nr runs, run[].first
+ * counted from sg - base): a run of more than one segment — in-sequence
+ * PSH|ACK segments with equal ack, payloads captured whole and byte-contiguous
+ * at the run's offset — makes one fragment of the run's bytes and one ACK,
+ * whose acknum is rcv_nxt after the run: the ACK that closes the run in the
+ * segment-by-segment order.  A run of one takes the segment's path.  A full
+ * receive ring drops whole runs.  Connections on the frame-by-frame path are
+ * never coalesced. */
+static int deliver_tcp_conn(struct tcp_stream *s, const rxg_segment *sg, uint32_t k,
+                            const rxg_tcp_run *run, uint32_t nr, uint32_t base,
+                            const uint8_t *payload, int32_t pl_ref, rxg_mbuf *const *m,
+                            uint8_t *handled, int *rc_out) {
+    if (conn_claim(s, sg, k, handled, rc_out)) return 1;
+    /* the fragments and ACKs the segments make, in order (the state changes
+     * at most once: ESTABLISHED -> CLOSE_WAIT on a FIN) */
+    uint32_t nfr = 0, nack = 0;
+    uint64_t pbytes = 0;
+    int st = s->status;
+    const int inpl = g_inplace; /* payloads captured whole stay in their frames */
+    uint32_t ri = 0; /* the run that holds segment j */
+    for (uint32_t j = 0; j < k && st == TCP_STATUS_ESTABLISHED; j++) {
+        if (run) {
+            while (ri + 1 < nr && run[ri + 1].first - base <= j) ri++;
+            if (run[ri].nseg > 1) { /* one fragment, one ACK for the run (j is its first) */
+                nfr++, nack++;
+                if (pl_ref < 0) pbytes += run[ri].bytes; /* (copied) */
+                g_gro_absorbed += run[ri].nseg - 1;
+                j += run[ri].nseg - 1;
+                continue;
+            }
+        }
+        if (sg[j].flags & TCP_PSH) {
+            nfr++, nack++;
+            if (sg[j].plen > 0 && (sg[j].ncopy != (uint32_t)sg[j].plen /* cut short */ ||
+                                   (!inpl && pl_ref < 0)))
+                pbytes += (uint64_t)sg[j].plen; /* (copied) */
+        }
+        if (sg[j].flags & TCP_FIN) nfr++, nack++, st = TCP_STATUS_CLOSE_WAIT;
+    }
+    if (!nfr) return 0;
+    struct conn_batch cb;
+    conn_open(&cb, s, nfr, nack, pbytes);
+    ri = 0;
+    for (uint32_t j = 0; j < k && s->status == TCP_STATUS_ESTABLISHED; j++) {
+        const rxg_segment *g = &sg[j];
+        if (run) {
+            while (ri + 1 < nr && run[ri + 1].first - base <= j) ri++;
+            if (run[ri].nseg > 1) { /* (j is the run's first segment) */
+                const rxg_tcp_run *r = &run[ri];
+                const struct frag_src x = {g, r->nseg, r->offset, r->bytes, r->bytes, 0, 0};
+                put_frag(&cb, &x, payload, pl_ref, m, 0);
+                s->rcv_nxt += r->bytes;
+                s->snd_nxt = g->ack;
+                put_ack(&cb, s, g);
+                j += r->nseg - 1;
+                continue;
+            }
+        }
+        if (g->flags & TCP_PSH) { /* tcp.c:226-262 */
+            const uint32_t len = g->plen > 0 ? (uint32_t)g->plen : 0u;
+            const struct frag_src x = {g, 1, g->offset, len, g->ncopy, 0, 0};
+            put_frag(&cb, &x, payload, pl_ref, m, inpl);
+            s->rcv_nxt += (uint32_t)g->plen;
+            s->snd_nxt = g->ack;
+            put_ack(&cb, s, g);
+        }
+        if (g->flags & TCP_FIN) { /* tcp.c:264-294: CLOSE_WAIT, EOF, ACK */
+            const struct frag_src eof = {g, 1, 0, 0, 0, 0, 0};
+            s->status = TCP_STATUS_CLOSE_WAIT;
+            put_frag(&cb, &eof, payload, pl_ref, m, 0);
+            s->rcv_nxt += 1;
+            s->snd_nxt = g->ack;
+            put_ack(&cb, s, g);
+        }
+    }
+    conn_close(&cb, s);
     if (st == TCP_STATUS_CLOSE_WAIT) restate_tcb(s, 0);
     return 0;
 }
 
-/* deliver_tcp_conn's stream form (stream assembly on): the connection's k
- * ordered records carry ncopy = take, and st[0..nst) are its streams
- * (st[].first counted from sg - base), each one a contiguous byte range at
- * st[].offset of the payload buffer.  The host rule of rxgpu.h ("TCP stream
- * assembly") aligns every stream with rcv_nxt: one receive fragment of the
- * fresh bytes (pointing into the held buffer when there is one, else copied;
- * host verdicts: gathered from the frames, each record's skip passed over),
- * the EOF fragment behind a FIN in sequence, and one ACK per stream; a stream
- * behind a hole only draws an ACK.  LISTEN / SYN_RCVD / LAST_ACK keep the
- * frame-by-frame path (tcp_dispatch validates each frame there). */
+/* The stream form (stream assembly on): the connection's k ordered records
+ * carry ncopy = take, and st[0..nst) are its streams (st[].first counted from
+ * sg - base), each one a contiguous byte range at st[].offset of the payload
+ * buffer.  The host rule of rxgpu.h ("TCP stream assembly") aligns every
+ * stream with rcv_nxt: one receive fragment of the fresh bytes (in the held
+ * buffer when there is one, else copied; host verdicts: gathered from the
+ * frames, each record's skip passed over), the EOF fragment behind a FIN in
+ * sequence, and one ACK per stream; a stream behind a hole only draws an ACK. */
 static int deliver_tcp_conn_streams(struct tcp_stream *s, const rxg_segment *sg, uint32_t k,
                                     const rxg_tcp_stream *st, uint32_t nst, uint32_t base,
                                     const uint8_t *payload, int32_t pl_ref, rxg_mbuf *const *m,
                                     uint8_t *handled, int *rc_out) {
-    if (s->status == TCP_STATUS_LISTEN || s->status == TCP_STATUS_SYN_RCVD ||
-        s->status == TCP_STATUS_LAST_ACK)
-        return 1;
-    for (uint32_t j = 0; j < k; j++) {
-        handled[sg[j].frame] = 1;
-        if (rc_out) rc_out[sg[j].frame] = RXG_RC_OK;
-    }
-    g_stat[2] += k;
+    if (conn_claim(s, sg, k, handled, rc_out)) return 1;
     if (s->status != TCP_STATUS_ESTABLISHED) return 0;
     /* the fragments and ACKs the streams make, in order */
     uint32_t nfr = 0, nack = 0, R = s->rcv_nxt;
@@ -2635,27 +2547,9 @@ static int deliver_tcp_conn_streams(struct tcp_stream *s, const rxg_segment *sg,
         }
     }
     if (!nack) return 0;
-    pthread_mutex_lock(&s->mutex);
-    const uint32_t rroom = s->rq < D_RING_SIZE ? D_RING_SIZE - s->rq : 0;
-    const uint32_t aroom = s->sq < D_RING_SIZE ? D_RING_SIZE - s->sq : 0;
-    const uint32_t rtake = nfr < rroom ? nfr : rroom, atake = nack < aroom ? nack : aroom;
-    struct frag_batch *rb = NULL, *ab = NULL;
-    if (rtake) rb = bp_alloc(sizeof(*rb) + rtake * sizeof(struct tcp_fragment) + pbytes + 1);
-    if (atake) ab = bp_alloc(sizeof(*ab) + atake * sizeof(struct tcp_fragment));
-    for (int w = 0; w < 2; w++) {
-        struct frag_batch *b = w ? ab : rb;
-        if (!b) continue;
-        memset(&b->item, 0, sizeof(b->item));
-        b->item.batch = b;
-        b->n = w ? atake : rtake;
-        b->next = 0;
-        b->frag = (struct tcp_fragment *)(b + 1);
-        b->pl_ref = -1;
-    }
-    unsigned char *pp = rb ? (unsigned char *)(rb->frag + rtake) : NULL;
-    uint32_t fi = 0, ai = 0;
-    int closed = 0;
-    for (uint32_t q = 0; q < nst && !closed; q++) {
+    struct conn_batch cb;
+    conn_open(&cb, s, nfr, nack, pbytes);
+    for (uint32_t q = 0; q < nst && s->status == TCP_STATUS_ESTABLISHED; q++) {
         const rxg_tcp_stream *x = &st[q];
         const rxg_segment *g = &sg[x->first - base], *gl = g + x->nseg - 1;
         const int fin = (x->flags & RXG_STREAM_FIN) != 0;
@@ -2672,93 +2566,26 @@ static int deliver_tcp_conn_streams(struct tcp_stream *s, const rxg_segment *sg,
         if (d >= 0) {
             const uint32_t fresh = x->bytes > (uint32_t)d ? x->bytes - (uint32_t)d : 0;
             g_asm_dup += x->bytes - fresh;
-            for (int eof = 0; eof < 2; eof++) {
-                if (eof ? !(fin && (uint32_t)d <= x->bytes) : !fresh) continue;
-                if (fi < rtake && rb) {
-                    struct tcp_fragment *fr = &rb->frag[fi];
-                    memset(fr, 0, sizeof(*fr));
-                    fr->dport = ntohs(g->dport);
-                    fr->sport = ntohs(g->sport);
-                    if (eof) {
-                        /* (the 0-length fragment: nrecv's EOF) */
-                    } else if (pl_ref >= 0) {
-                        fr->data = (unsigned char *)payload + x->offset + (uint32_t)d; /* (no copy) */
-                        fr->length = fresh;
-                        rb->pl_ref = pl_ref;
-                    } else {
-                        fr->data = pp;
-                        fr->length = fresh;
-                        if (payload) {
-                            memcpy(pp, payload + x->offset + (uint32_t)d, fresh);
-                        } else { /* (host verdicts: from the frames, skip passed over) */
-                            uint32_t pos = 0;
-                            for (uint32_t j = 0; j < x->nseg; j++) {
-                                const uint32_t t = g[j].ncopy, lo = pos > (uint32_t)d ? pos : (uint32_t)d;
-                                if (pos + t > lo) {
-                                    const rxg_mbuf *mb_ = m[g[j].frame];
-                                    memcpy(pp + (lo - (uint32_t)d),
-                                           (const uint8_t *)mb_->buf_addr + mb_->data_off + 34u +
-                                               4u * g[j].hl + ((uint32_t)g[j].plen - t) + (lo - pos),
-                                           pos + t - lo);
-                                }
-                                pos += t;
-                            }
-                        }
-                        pp += fresh;
-                        g_copied_bytes += fresh;
-                    }
-                    g_stat[4]++;
-                } else {
-                    g_stat[1]++;
-                }
-                fi++;
-                if (eof) {
-                    s->status = TCP_STATUS_CLOSE_WAIT;
-                    s->rcv_nxt += 1;
-                    closed = 1;
-                } else {
-                    s->rcv_nxt += fresh;
-                }
+            if (fresh) {
+                const uint32_t skip = (uint32_t)d;
+                const struct frag_src f = {g, x->nseg, x->offset + skip, fresh, fresh, skip, 1};
+                put_frag(&cb, &f, payload, pl_ref, m, 0);
+                s->rcv_nxt += fresh;
+            }
+            if (fin && (uint32_t)d <= x->bytes) {
+                const struct frag_src eof = {g, 1, 0, 0, 0, 0, 0};
+                put_frag(&cb, &eof, payload, pl_ref, m, 0);
+                s->status = TCP_STATUS_CLOSE_WAIT;
+                s->rcv_nxt += 1;
             }
             s->snd_nxt = x->ack;
         } else {
             g_asm_hole++;
         }
-        if (ai < atake && ab) { /* ng_tcp_send_ackpkt, tcp.c:187-216 */
-            struct tcp_fragment *a = &ab->frag[ai];
-            memset(a, 0, sizeof(*a));
-            a->sport = gl->dport;
-            a->dport = gl->sport;
-            a->seqnum = s->snd_nxt;
-            a->acknum = s->rcv_nxt;
-            a->tcp_flags = TCP_ACK;
-            a->windows = D_TCP_INITIAL_WINDOW;
-            a->hdrlen_off = 0x50;
-        }
-        ai++;
+        put_ack(&cb, s, gl);
     }
-    if (rb) {
-        if (rb->pl_ref >= 0) { /* until the batch is freed */
-            rxg_payload_hold(g_ctx, rb->pl_ref);
-            atomic_fetch_add_explicit(&g_pl_batches, 1, memory_order_relaxed);
-            atomic_fetch_add_explicit(&g_pl_out[rb->pl_ref], 1, memory_order_relaxed);
-        }
-        if (ring_enqueue(s->rcvbuf, &rb->item)) { /* (not reached: items <= fragments <= capacity) */
-            frag_item_free(&rb->item);
-            g_stat[4] -= rtake, g_stat[1] += rtake;
-        } else {
-            cnt_set(&s->rq, s->rq + rtake);
-            pthread_cond_signal(&s->cond); /* tcp.c:178-180 */
-        }
-    }
-    if (ab) {
-        if (ring_enqueue(s->sndbuf, &ab->item))
-            bp_free(ab);
-        else
-            cnt_set(&s->sq, s->sq + atake);
-    }
-    pthread_mutex_unlock(&s->mutex);
-    if (closed) restate_tcb(s, 0);
+    conn_close(&cb, s);
+    if (s->status == TCP_STATUS_CLOSE_WAIT) restate_tcb(s, 0);
     return 0;
 }
 
@@ -2796,10 +2623,11 @@ static void deliver_tcp_sorted(const rxg_segment *sg, uint32_t nseg, const rxg_t
     }
 }
 
-/* The segment records of a burst whose verdicts came from elsewhere
- * (nstack_deliver): the same fields the GPU's segment sort decodes (rc-0 TCP
- * verdicts naming a live tcb id, bytes past the capture read as 0), stably
- * sorted by tcb id on the host; payloads are then copied from the frames */
+/* ---- the host record pipeline (nstack_deliver) ----------------------------
+ * The segment records of a burst whose verdicts came from elsewhere: the same
+ * fields the GPU's segment sort decodes (rc-0 TCP verdicts naming a live tcb
+ * id, bytes past the capture read as 0), stably sorted by tcb id on the host;
+ * payloads are then copied from the frames */
 static int seg_cmp(const void *a, const void *b) {
     const rxg_segment *x = a, *y = b;
     if (x->flow != y->flow) return x->flow < y->flow ? -1 : 1;
@@ -2833,6 +2661,135 @@ static uint32_t host_segments(rxg_mbuf *const *m, uint32_t n, const rxg_verdict 
     return k;
 }
 
+/* What the device paths get from the library for deliver_tcp_sorted, built
+ * on the host by the rules' host restatements: the sorted records; with
+ * ordering or assembly on, in sequence order (assembly implies ordering);
+ * with coalescing on, the runs; with assembly on, the streams, the records
+ * then carrying ncopy = take as the device's do. */
+struct host_records {
+    rxg_segment *sg;
+    uint32_t nseg;
+    rxg_tcp_run *run; /* NULL: the segments one by one */
+    uint32_t nrun;
+    rxg_tcp_stream *stm;
+    struct asm_view av; /* av.st NULL: assembly off */
+};
+static void host_records_free(struct host_records *hr) {
+    free(hr->sg), free(hr->run), free(hr->stm);
+    memset(hr, 0, sizeof(*hr));
+}
+/* Returns 0, or -1 (nothing left allocated) when memory ran out or a rule
+ * refused the records: every TCP frame of the burst then takes the
+ * frame-by-frame path, which validates it on its own. */
+static int host_records_build(struct host_records *hr, rxg_mbuf *const *m, uint32_t n,
+                              const rxg_verdict *v) {
+    memset(hr, 0, sizeof(*hr));
+    if (!(hr->sg = malloc((size_t)n * sizeof(*hr->sg)))) return -1;
+    rxg_segment *sg = hr->sg;
+    const uint32_t k = hr->nseg = host_segments(m, n, v, sg);
+    if (!k || !(g_gro || g_order || g_assemble)) return 0;
+    /* the rules' side arrays: the source addresses (read from the mbufs),
+     * then 4k words of scratch (ordering: perm, sipo; assembly: avail and the
+     * rule's three outputs) and the ordered copy of the records */
+    uint32_t *sip = malloc((size_t)k * 5 * sizeof(*sip)), *w = sip ? sip + k : NULL;
+    rxg_segment *so = g_order || g_assemble ? malloc((size_t)k * sizeof(*so)) : NULL;
+    if (g_gro) hr->run = malloc((size_t)k * sizeof(*hr->run));
+    if (g_assemble) hr->stm = malloc((size_t)k * sizeof(*hr->stm));
+    int ok = sip && (so || !(g_order || g_assemble)) && (hr->run || !g_gro) &&
+             (hr->stm || !g_assemble);
+    if (ok) {
+        for (uint32_t j = 0; j < k; j++) {
+            const rxg_mbuf *mb = m[sg[j].frame];
+            const uint8_t *f = (const uint8_t *)mb->buf_addr + mb->data_off;
+            sip[j] = 0;
+            for (uint32_t q = 0; q < 4; q++)
+                if (26u + q < mb->data_len) sip[j] |= (uint32_t)f[26u + q] << (8u * q);
+        }
+        uint32_t moved = 0, *perm = w, *sipo = w + k;
+        if (so && rxg_tcp_order_host(sg, sip, k, perm, &moved) == RXG_OK && moved) {
+            for (uint32_t j = 0; j < k; j++) so[j] = sg[perm[j]], sipo[j] = sip[perm[j]];
+            memcpy(sg, so, (size_t)k * sizeof(*sg));
+            memcpy(sip, sipo, (size_t)k * sizeof(*sip));
+            g_order_moved += moved;
+        }
+        if (hr->run && rxg_tcp_runs_host(sg, sip, k, g_gro, hr->run, &hr->nrun) != RXG_OK)
+            hr->nrun = 0;
+        if (hr->stm) {
+            for (uint32_t j = 0; j < k; j++) {
+                const uint32_t cap = m[sg[j].frame]->data_len, from = 34u + 4u * sg[j].hl;
+                w[j] = cap > from ? cap - from : 0u;
+            }
+            uint32_t nst = 0;
+            ok = rxg_tcp_assemble_host(sg, sip, w, k, hr->stm, &nst, w + k, w + 2 * k, w + 3 * k) ==
+                 RXG_OK;
+            for (uint32_t j = 0; ok && j < k; j++) sg[j].ncopy = (uint16_t)w[2 * k + j];
+            hr->av.st = hr->stm, hr->av.n = nst;
+        }
+    }
+    free(sip), free(so);
+    if (!ok) host_records_free(hr);
+    return ok ? 0 : -1;
+}
+
+/* ---- the burst-scoped state (g_lock held) ---------------------------------
+ * burst_begin: the verdicts were made against the lists of generation gen
+ * (another one: stale, every frame is looked up again); SYN cookies as the
+ * alarm stood before this burst, no statuses yet.  burst_end: all of it, and
+ * the mark that UDP went out as batches, cleared for the next burst. */
+static void burst_begin(uint64_t gen) {
+    g_burst_mutated = 0;
+    g_burst_stale = gen != g_snap_gen;
+    g_ck_on = ck_active();
+    g_ck_st = NULL;
+    if (g_ck_on) g_ck_p.t = ck_now();
+}
+static void burst_end(void) {
+    g_udp_done = 0;
+    g_burst_stale = 0;
+    g_ck_on = 0, g_ck_st = NULL;
+}
+
+int nstack_deliver(rxg_mbuf *const *m, uint32_t n, const rxg_verdict *v, uint64_t gen,
+                   int *rc_out) {
+    if (!m || !v) return n ? RXG_EINVAL : 0;
+    reclaim();
+    pthread_mutex_lock(&g_lock);
+    /* (refused while pipelined bursts are pending: their frames come first) */
+    int rc = g_ctx && !g_pend_n ? RXG_OK : RXG_EINVAL;
+    int delivered = 0;
+    if (rc == RXG_OK) {
+        burst_begin(gen);
+        /* fresh: the verdicts' flow ids name the live blocks */
+        const int fresh = !g_burst_stale && n;
+        if (g_ck_on && fresh) ck_host_burst(m, n, v);
+        if (g_ddos && n) ddos_host_burst(m, n); /* (sees the frames; changes nothing below) */
+        if (g_l2 && n) l2_host_frames(m, n, v);  /* (the rule reads cls alone: stale or not) */
+        rxg_dgram *dg = NULL;
+        uint32_t *first = NULL;
+        uint8_t *pl = NULL;
+        if (fresh && host_dgrams(m, n, v, s_udp_cap, &dg, &first, &pl)) {
+            delivered += deliver_udp_batches(m, dg, first, pl, s_udp_cap);
+            g_udp_done = 1; /* the per-frame loop leaves UDP alone */
+        }
+        free(dg), free(first), free(pl);
+        const uint8_t *done = NULL;
+        struct host_records hr;
+        if (fresh && !grow((void **)&s_handled, &s_handled_cap, n, 1) &&
+            !host_records_build(&hr, m, n, v)) {
+            memset(s_handled, 0, n);
+            deliver_tcp_sorted(hr.sg, hr.nseg, hr.nrun ? hr.run : NULL, hr.nrun,
+                               hr.av.st ? &hr.av : NULL, NULL, -1, m, s_handled, rc_out);
+            host_records_free(&hr);
+            done = s_handled;
+        }
+        delivered += deliver_burst(m, n, v, rc_out, done);
+        burst_end();
+        atomic_fetch_add_explicit(&g_deliveries, 1, memory_order_release);
+    }
+    pthread_mutex_unlock(&g_lock);
+    return rc == RXG_OK ? delivered : rc;
+}
+
 /* the last nstack_rx_burst's phases (nstack_last_burst_phases) */
 static float g_phase_ms[12];
 
@@ -2840,6 +2797,21 @@ static double mono_ms(void) {
     struct timespec ts;
     clock_gettime(CLOCK_MONOTONIC, &ts);
     return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
+}
+
+/* a delivered burst's phases: the device's five (HIP events; two halves
+ * summed), the library calls (host clock), deliver_part's three, the call
+ * since t0, the burst's segment and datagram records */
+static void phases_record(const float *gms, const float *gms2, double lib_ms, const double ph[3],
+                          double t0, const rxg_delivery *d, const rxg_delivery *d2) {
+    for (int j = 0; j < 5; j++) g_phase_ms[j] = gms[j] + (gms2 ? gms2[j] : 0.0f);
+    g_phase_ms[5] = (float)lib_ms;
+    g_phase_ms[6] = (float)ph[0]; /* UDP batches to the sockets */
+    g_phase_ms[7] = (float)ph[1]; /* TCP connections from the segment sort */
+    g_phase_ms[8] = (float)ph[2]; /* the frame-by-frame loop (the rest) */
+    g_phase_ms[9] = (float)(mono_ms() - t0);
+    g_phase_ms[10] = (float)(d->nseg + (d2 ? d2->nseg : 0));
+    g_phase_ms[11] = (float)(d->ndgram + (d2 ? d2->ndgram : 0));
 }
 
 /* a pooled payload buffer the library can take for the next submit (set
@@ -2905,8 +2877,7 @@ static int deliver_part(rxg_mbuf *const *m, uint32_t k, const rxg_verdict *v, ui
                         int *rco, rxg_delivery *d, uint64_t gen0, double ph[3]) {
     int delivered = 0;
     const double t1 = mono_ms();
-    g_burst_mutated = 0;
-    g_burst_stale = gen0 != g_snap_gen;
+    burst_begin(gen0);
     if (g_burst_stale) { /* (ids may name other blocks now) */
         d->first = NULL, d->nseg = 0;
         g_stale_parts++;
@@ -2922,15 +2893,11 @@ static int deliver_part(rxg_mbuf *const *m, uint32_t k, const rxg_verdict *v, ui
     if (d->nseg && g_gro && rxg_delivery_runs(g_ctx, d, &run, &nrun) != RXG_OK) run = NULL, nrun = 0;
     uint32_t moved = 0; /* (ordering on at the submit: the records that moved) */
     if (d->nseg && (g_order || g_assemble) && rxg_delivery_moved(g_ctx, d, &moved) == RXG_OK) g_order_moved += moved;
-    /* SYN cookies on (the alarm as it stood before this burst): the burst's
-     * statuses, descriptors and totals when K7 ran at the submit and the
-     * verdicts' ids still name the live blocks */
-    g_ck_on = ck_active();
-    g_ck_st = NULL;
+    /* SYN cookies on: the burst's statuses, descriptors and totals when K7 ran
+     * at the submit and the verdicts' ids still name the live blocks */
     if (g_ck_on) {
         const rxg_txd *ctxd = NULL;
         uint32_t cn = 0, ctot[4];
-        g_ck_p.t = ck_now();
         if (!g_burst_stale && rxg_delivery_cookies(g_ctx, d, &g_ck_st, &ctxd, &cn, ctot) == RXG_OK &&
             g_ck_st)
             ck_take(ctxd, ctot);
@@ -2959,9 +2926,7 @@ static int deliver_part(rxg_mbuf *const *m, uint32_t k, const rxg_verdict *v, ui
                            d->tcp_payload, d->tcp_payload_ref, m, handled, rco);
     const double t3 = mono_ms();
     delivered += deliver_burst(m, k, v, rco, handled);
-    g_udp_done = 0;
-    g_burst_stale = 0;
-    g_ck_on = 0, g_ck_st = NULL;
+    burst_end();
     const double t4 = mono_ms();
     ph[0] += t2 - t1, ph[1] += t3 - t2, ph[2] += t4 - t3;
     return delivered;
@@ -3059,14 +3024,7 @@ int nstack_rx_burst(rxg_mbuf *const *m, uint32_t n, int *rc_out, rxg_verdict *v_
     }
     if (rc == RXG_OK || partial) {
         if (v_out) memcpy(v_out, s_v, (size_t)(partial ? nh : n) * sizeof(rxg_verdict));
-        for (int j = 0; j < 5; j++) g_phase_ms[j] = gms[0][j] + gms[1][j];
-        g_phase_ms[5] = (float)lib_ms;   /* the library calls (host clock) */
-        g_phase_ms[6] = (float)ph[0];    /* UDP batches to the sockets */
-        g_phase_ms[7] = (float)ph[1];    /* TCP connections from the segment sort */
-        g_phase_ms[8] = (float)ph[2];    /* the frame-by-frame loop (the rest) */
-        g_phase_ms[9] = (float)(mono_ms() - t0); /* the whole call */
-        g_phase_ms[10] = (float)(d[0].nseg + (parts > 1 ? d[1].nseg : 0));
-        g_phase_ms[11] = (float)(d[0].ndgram + (parts > 1 ? d[1].ndgram : 0));
+        phases_record(gms[0], gms[1], lib_ms, ph, t0, &d[0], parts > 1 ? &d[1] : NULL);
     }
     if (done[0]) atomic_fetch_add_explicit(&g_deliveries, 1, memory_order_release);
     pthread_mutex_unlock(&g_lock);
@@ -3162,14 +3120,7 @@ int nstack_rx_complete(void) {
     double ph[3] = {0, 0, 0};
     const int delivered = deliver_part(p->m, p->n, p->v, p->handled, p->rc_out, &p->d, p->gen0, ph);
     if (p->v_out) memcpy(p->v_out, p->v, (size_t)p->n * sizeof(rxg_verdict));
-    for (int j = 0; j < 5; j++) g_phase_ms[j] = gms[j];
-    g_phase_ms[5] = (float)lib_ms;
-    g_phase_ms[6] = (float)ph[0];
-    g_phase_ms[7] = (float)ph[1];
-    g_phase_ms[8] = (float)ph[2];
-    g_phase_ms[9] = (float)(mono_ms() - t0); /* this call (the submit is the caller's) */
-    g_phase_ms[10] = (float)p->d.nseg;
-    g_phase_ms[11] = (float)p->d.ndgram;
+    phases_record(gms, NULL, lib_ms, ph, t0 /* (the submit is the caller's) */, &p->d, NULL);
     atomic_fetch_add_explicit(&g_deliveries, 1, memory_order_release);
     pthread_mutex_unlock(&g_lock);
     return delivered;
